@@ -3,14 +3,20 @@
 batch-8 3x1024x1024 RGB deconvolution, sum_squares(conv(x,psf)-b) + norm1(grad_H x) + norm1(grad_W x),
 FFT-diagonalised x-update + L1-TV prox -- through the drop-in `dprox` API on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A "step" is ONE ADMM iteration over one per-GPU batch of 8 images, inputs resident in HBM.  With N
 GPUs every rank solves its own independent batch of 8 (weak scaling, no data-path collective: the
-images of a batch never interact); `value` = N*K / max-over-ranks time.
+images of a batch never interact); `value` = N*K / max-over-ranks time, `ms_per_step` = the time of
+one timed step.
 
-The JSON line also carries
+A plain run measures the headline only: set-up, the load leg and W warm-up steps the headline protocol
+puts in front of the timed region, exactly K timed steps, the JSON line.  --dump-outputs DIR writes
+what the last timed step left -- the solver state x, v_0, v_1, u_0, u_1 of rank 0 -- as DIR/<name>.npy (float32,
+the same seeded sample of 2^21 entries of each; inputs are seeded, so two builds compare entry for entry).
+
+With --full the JSON line also carries
   roofline     : dominant kernel's algorithmic bytes per launch / its average duration measured with
                  HIP events on the launch stream (second pass of K iterations with the library's
                  per-kernel timers on), against 8 TB/s HBM3E;
@@ -70,6 +76,11 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the state the last timed step computed as DIR/<name>.npy "
+                    "(a fixed, seeded sample of each array)")
+    ap.add_argument("--full", action="store_true", help="run every companion leg as well (cold / warm solves, steady state, idle-GPU "
+                    "region, roofline and counter passes, quality, CPU baseline, other configurations, strong scaling); the --no-* and "
+                    "--pmc switches below apply to it")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extra-configs", action="store_true")
     ap.add_argument("--pmc", dest="pmc", action="store_true", default=None, help="measure roofline.traffic in this run: two rocprofv3 --pmc passes "
@@ -98,6 +109,55 @@ def make_problem(dp, synthetic, rank, device):
 def psnr_per_image(out, gt):
     mse = ((out - gt) ** 2).reshape(out.shape[0], -1).mean(dim=1)
     return (10.0 * torch.log10(1.0 / mse)).tolist()
+
+
+DUMP_SAMPLES = 1 << 21          # entries per dumped array: 5 arrays x 8 MiB, within the 64 MB --dump-outputs allows
+
+
+def dump_outputs(d, state):
+    """the state iters() returned after the last timed step -- (x, [v_i], [u_i]), each [B, C, H, W] float32 -- as d/x.npy, d/v0.npy, ...:
+    the same fixed sample of DUMP_SAMPLES flat indices of every array (sorted, numpy default_rng(0)), float32"""
+    x, v, u = state
+    arrays = {"x": x, **{f"v{i}": t for i, t in enumerate(v)}, **{f"u{i}": t for i, t in enumerate(u)}}
+    idx = np.sort(np.random.default_rng(0).choice(x.numel(), size=min(x.numel(), DUMP_SAMPLES), replace=False))
+    idx_d = torch.from_numpy(idx).to(x.device)
+    os.makedirs(d, exist_ok=True)
+    for name, t in arrays.items():
+        np.save(os.path.join(d, name + ".npy"), t.reshape(-1).index_select(0, idx_d).float().cpu().numpy())
+
+
+def emit(res):
+    """the one JSON line.  RCCL writes a version banner to the C stdout buffer, which would otherwise be flushed at exit BEHIND the JSON
+    line: flush it first, print the line, then close stdout for everything that follows"""
+    ctypes.CDLL(None).fflush(None)
+    sys.stdout.write(json.dumps(res) + "\n")
+    sys.stdout.flush()
+    os.dup2(os.open(os.devnull, os.O_WRONLY), 1)
+
+
+def headline(world, K, Wm, dt):
+    """the keys of the JSON line a plain run prints; --full adds its legs' figures to them"""
+    return {
+        "metric": "admm_iters_per_sec", "value": world * K / dt, "unit": "it/s (one iteration = one 8x3x1024x1024 batch)",
+        "n_gpus": world, "steps": K, "warmup": Wm, "ms_per_step": 1e3 * dt / K, "higher_is_better": True,
+        "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+        "scaling_note": "`value` is WEAK scaling: every rank solves its own batch of 8 (N x the work, ~N x the rate by construction).  The STRONG-scaling "
+                        "figures north_star's '>= 6x at 8 GPUs' is about -- one fixed batch dealt over the ranks -- are `sharded.<config>.speedup_vs_n1` "
+                        "(loop = iterations on resident slices, end_to_end = incl. scatter and all-gather), present for N > 1 with --full",
+        "config": {"workload": "config 2: batch-8 3x1024x1024 RGB deconv, sum_squares(conv(x,psf)-b)+norm1(grad_H)+norm1(grad_W), "
+                               "ADMM rho=0.1 lam=0.005, Gaussian 15/5 PSF",
+                   "batch_per_gpu": B, "global_batch": B * world, "shape": [C, H, W], "parallelism": f"batch-shard x{world}"},
+        "headline_protocol": {"warmup": Wm, "timed_steps": K, "runs_directly_after": "the steady-state leg (W warm-up + 200 timed steps, ~40 ms of load; "
+                                                                                    "its figure is `steady_state` with --full)",
+                              "note": "`value`: W warm-up steps, then exactly K timed steps between barriers; the region follows the steady-state "
+                                      "measurement without host work in between, i.e. on a GPU that has just been under load.  "
+                                      "`value_after_idle_gpu` (--full): the identical region after the GPU idled for 0.5 s in front of the warm-up -- this GPU "
+                                      "needs tens of ms of load to reach its clocks, so a 5-step warm-up (1 ms) leaves the ramp inside the "
+                                      "timed steps.  `steady_state` (--full): 200 timed steps.",
+                              "clock": "opening: torch.cuda.synchronize + inter-rank barrier + synchronize, then t0; closing: torch.cuda.synchronize, "
+                                       "then t1, then the inter-rank barrier; the job's time is the MAX of t1 - t0 over the ranks (N = 1: no barrier).  "
+                                       "The closing RCCL barrier itself (~1 ms with the nccl backend) is not inside any rank's clock"},
+    }
 
 
 def timing_report(be):
@@ -605,7 +665,7 @@ def main():
     sched = {n: (rhos[..., :n].contiguous(), {k: v[..., :n].contiguous() for k, v in lams.items()}) for n in {K, 200}}
 
     def timed_region(n_steps):
-        """W untimed warm-up steps, then exactly n_steps timed steps between barriers"""
+        """W untimed warm-up steps, then exactly n_steps timed steps between barriers -> (seconds, the state iters() returned)"""
         solver.solve(x0=b, rhos=RHO, lams=LAM, max_iter=max(Wm, 1))
         st = solver.initialize(b)
         rs, ls = sched[n_steps]
@@ -622,34 +682,50 @@ def main():
             t = torch.tensor([dt_], device=device, dtype=torch.float64)
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             dt_ = float(t.item())
-        return dt_
+        return dt_, st
 
-    # ---- leg 1, cold solve: BASELINE.json config 2 as stated -- compile()d solver, nothing cached (OTF / denominator tables, fp64
-    #      data spectrum, workspaces are all built inside), 50 iterations, wall clock around solve().  Its result is the quality figure.
-    barrier()
-    t0 = time.perf_counter()
-    out = solver.solve(x0=b, rhos=RHO, lams=LAM, max_iter=50)
-    barrier()
-    cold_ms = 1e3 * (time.perf_counter() - t0)
-    assert solver.last_path == "fused", "bench must run the fused HIP iteration"
+    if a.full:
+        # ---- leg 1, cold solve: BASELINE.json config 2 as stated -- compile()d solver, nothing cached (OTF / denominator tables, fp64
+        #      data spectrum, workspaces are all built inside), 50 iterations, wall clock around solve().  Its result is the quality figure.
+        barrier()
+        t0 = time.perf_counter()
+        out = solver.solve(x0=b, rhos=RHO, lams=LAM, max_iter=50)
+        barrier()
+        cold_ms = 1e3 * (time.perf_counter() - t0)
+        assert solver.last_path == "fused", "bench must run the fused HIP iteration"
 
-    # (the roofline leg below runs as one chain: its data spectrum -- a layout of its own -- is computed here, not between the timed legs)
-    _env = os.environ.get("DPX_CHAINS")
-    os.environ["DPX_CHAINS"] = "1"
-    solver.solve(x0=b, rhos=RHO, lams=LAM, max_iter=2)
-    if _env is None:
-        os.environ.pop("DPX_CHAINS", None)
-    else:
-        os.environ["DPX_CHAINS"] = _env
+        # (the roofline leg below runs as one chain: its data spectrum -- a layout of its own -- is computed here, not between the timed legs)
+        _env = os.environ.get("DPX_CHAINS")
+        os.environ["DPX_CHAINS"] = "1"
+        solver.solve(x0=b, rhos=RHO, lams=LAM, max_iter=2)
+        if _env is None:
+            os.environ.pop("DPX_CHAINS", None)
+        else:
+            os.environ["DPX_CHAINS"] = _env
     # ---- leg 2, steady state: 200 timed steps (a solve's fixed parts -- seed pass, result emission, launch latency of the first
-    #      kernel -- spread over 200 iterations)
-    dt_steady = timed_region(200)
+    #      kernel -- spread over 200 iterations).  A plain run runs it too but reports nothing of it: it is the load the headline
+    #      region is defined to follow (headline_protocol).
+    dt_steady, st = timed_region(200)
     K_steady = 200
     # ---- leg 3, the headline: W warm-up steps, then exactly K timed steps.  It follows leg 2 directly (no host work in between), so
     #      the GPU has been under load for ~40 ms when the warm-up starts.  This GPU needs tens of milliseconds of sustained load to
     #      reach its clocks and loses them within a few milliseconds of idling (tools/ramp_probe.py): the last leg shows what the
     #      same region measures when the GPU idled in front of the W warm-up steps.
-    dt = timed_region(K) if K != 200 else dt_steady
+    if K != 200:
+        dt, st = timed_region(K)
+    else:
+        dt = dt_steady
+    assert solver.last_path == "fused", "bench must run the fused HIP iteration"
+    final_state = st if a.dump_outputs else None           # (the last timed step's state, written out behind the timed legs)
+    del st
+    if not a.full:
+        if rank == 0:
+            if a.dump_outputs:
+                dump_outputs(a.dump_outputs, final_state)
+            emit(headline(world, K, Wm, dt))
+        if dist is not None:
+            dist.destroy_process_group()
+        return
     # ---- roofline leg: the same K iterations once more with the library's per-kernel timers on (HIP events attached to the dispatch
     #      packets), directly behind the headline region -- same clocks
     #      With sub-batch chains (dprox/algo/fused.py: two halves of the batch iterate independently on two streams) two launches share
@@ -701,7 +777,7 @@ def main():
     cold2_ms = min(cold_runs)
     # ---- leg 6 (last): the same region after the GPU idled for half a second (the clock ramp falls into the timed steps)
     time.sleep(0.5)
-    dt_idle = timed_region(K)
+    dt_idle, _ = timed_region(K)
 
     # ---- quality (of the cold 50-iteration solve) -------------------------------------
     psnr_in, psnr_out = psnr_per_image(b, gt), psnr_per_image(out, gt)
@@ -788,25 +864,8 @@ def main():
     dom_avg_s = 1e-3 * rep[dom][1] / rep[dom][0]
     achieved = dom_bytes / dom_avg_s
     it_per_s = world * K / dt
-    res = {
-        "metric": "admm_iters_per_sec", "value": it_per_s, "unit": "it/s (one iteration = one 8x3x1024x1024 batch)",
-        "n_gpus": world, "steps": K, "warmup": Wm, "ms_per_step": 1e3 * dt / K, "higher_is_better": True,
-        "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-        "scaling_note": "`value` is WEAK scaling: every rank solves its own batch of 8 (N x the work, ~N x the rate by construction).  The STRONG-scaling "
-                        "figures north_star's '>= 6x at 8 GPUs' is about -- one fixed batch dealt over the ranks -- are `sharded.<config>.speedup_vs_n1` "
-                        "(loop = iterations on resident slices, end_to_end = incl. scatter and all-gather), present for N > 1",
-        "config": {"workload": "config 2: batch-8 3x1024x1024 RGB deconv, sum_squares(conv(x,psf)-b)+norm1(grad_H)+norm1(grad_W), "
-                               "ADMM rho=0.1 lam=0.005, Gaussian 15/5 PSF",
-                   "batch_per_gpu": B, "global_batch": B * world, "shape": [C, H, W], "parallelism": f"batch-shard x{world}"},
-        "headline_protocol": {"warmup": Wm, "timed_steps": K, "runs_directly_after": "the steady-state leg (steady_state: W warm-up + 200 timed steps, ~40 ms of load)",
-                              "note": "`value`: W warm-up steps, then exactly K timed steps between barriers; the region follows the steady-state "
-                                      "measurement without host work in between, i.e. on a GPU that has just been under load.  "
-                                      "`value_after_idle_gpu`: the identical region after the GPU idled for 0.5 s in front of the warm-up -- this GPU "
-                                      "needs tens of ms of load to reach its clocks, so a 5-step warm-up (1 ms) leaves the ramp inside the "
-                                      "timed steps.  `steady_state`: 200 timed steps.",
-                              "clock": "opening: torch.cuda.synchronize + inter-rank barrier + synchronize, then t0; closing: torch.cuda.synchronize, "
-                                       "then t1, then the inter-rank barrier; the job's time is the MAX of t1 - t0 over the ranks (N = 1: no barrier).  "
-                                       "The closing RCCL barrier itself (~1 ms with the nccl backend) is not inside any rank's clock"},
+    res = headline(world, K, Wm, dt)
+    res.update({
         "value_after_idle_gpu": world * K / dt_idle, "ms_per_step_after_idle_gpu": 1e3 * dt_idle / K,
         "steady_state": {"steps": K_steady, "it_per_s": world * K_steady / dt_steady, "ms_per_step": 1e3 * dt_steady / K_steady,
                          "roofline_iteration_frac": (K_steady / dt_steady) * DESIGN_BYTES_PER_ELEM * n_elem / HBM_PEAK},
@@ -851,7 +910,7 @@ def main():
                                "survey_accounting_note": "comparison only: SURVEY 8(d) budgets 64 B/element for an un-fused 5-kernel "
                                                          "schedule; this schedule does not move those bytes"},
         "kernels": kernels,
-    }
+    })
     if world == 1 and not a.no_cpu_baseline:
         n_it, sb = 4, 2
         x_ref, res["cpu_baseline"] = cpu_baseline(b.cpu(), psf, n_iters=n_it, sample_b=sb)
@@ -902,12 +961,9 @@ def main():
         "note": "iteration fractions: it/s x 36 B/element x 25 165 824 elements / 8 TB/s (wall clock, chains on); `frac` of this object: the dominant "
                 "kernel alone, one chain; after_idle: the identical K-step region after the GPU idled 0.5 s in front of its warm-up",
     }
-    # RCCL writes a version banner to the C stdout buffer, which would otherwise be flushed at exit BEHIND the JSON line: flush it
-    # first, print the one line, then close stdout for everything that follows
-    ctypes.CDLL(None).fflush(None)
-    sys.stdout.write(json.dumps(res) + "\n")
-    sys.stdout.flush()
-    os.dup2(os.open(os.devnull, os.O_WRONLY), 1)
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, final_state)
+    emit(res)
     if stalled:
         os._exit(0)                                        # (a collective of the companion runs is still pending: no orderly teardown)
     if dist is not None:

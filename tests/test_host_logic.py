@@ -281,3 +281,22 @@ def test_product_does_not_import_the_oracle():
     for dirpath, _, files in os.walk(os.path.join(ROOT, "delta-prox_amd", "dprox")):
         src += [open(os.path.join(dirpath, f)).read() for f in files if f.endswith(".py")]
     assert not any(re.search(r"^\s*(import|from)\s+oracle", s, re.M) for s in src)
+
+
+def test_bench_dump_outputs_writes_the_same_sample_of_every_state_array(tmp_path):
+    """bench.py --dump-outputs: x and every v_i / u_i of the state as float32 <name>.npy, the same seeded entries of each in every run,
+    within the 64 MB the option allows for the headline's five arrays"""
+    import bench
+    x = torch.randn(2, 3, 1024, 1024, generator=torch.Generator().manual_seed(0))
+    state = (x, [x + 1, x + 2], [x + 3, x + 4])
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), state)
+    names = ["x", "v0", "v1", "u0", "u1"]
+    assert sorted(os.listdir(tmp_path / "a")) == sorted(n + ".npy" for n in names)
+    idx = np.sort(np.random.default_rng(0).choice(x.numel(), bench.DUMP_SAMPLES, replace=False))
+    for i, n in enumerate(names):
+        got = np.load(tmp_path / "a" / (n + ".npy"))
+        assert got.dtype == np.float32 and got.shape == (bench.DUMP_SAMPLES,)
+        np.testing.assert_array_equal(got, np.load(tmp_path / "b" / (n + ".npy")))
+        np.testing.assert_array_equal(got, (x + i).numpy().ravel()[idx])
+    assert len(names) * bench.DUMP_SAMPLES * 4 <= 64e6

@@ -3,10 +3,10 @@
 tag=${1:-r6}
 cd $GRAFT_REPO_ROOT && export TMPDIR=/tmp
 out=gpurun_out/prof_$tag; mkdir -p $out
-python bench.py > $out/bench.json 2> $out/bench.err
-python bench.py --steps 20 --warmup 5 > $out/bench_steps20_warmup5.json 2>> $out/bench.err
+python bench.py --full > $out/bench.json 2> $out/bench.err
+python bench.py --full --steps 20 --warmup 5 > $out/bench_steps20_warmup5.json 2>> $out/bench.err
 # kernel trace of the driver's command (config 2 only, one chain: every launch has the GPU to itself)
-rocprofv3 --kernel-trace --stats -d $out/kt -o kt --output-format csv -- python bench.py --steps 20 --warmup 5 --no-pmc --no-cpu-baseline --no-extra-configs --chains 1 > $out/bench_under_rocprof.json 2> $out/rocprof.err
+rocprofv3 --kernel-trace --stats -d $out/kt -o kt --output-format csv -- python bench.py --full --steps 20 --warmup 5 --no-pmc --no-cpu-baseline --no-extra-configs --chains 1 > $out/bench_under_rocprof.json 2> $out/rocprof.err
 cp $(find $out/kt -name "*kernel_stats.csv" | head -1) $out/kernel_stats.csv; rm -rf $out/kt
 for c in FETCH_SIZE WRITE_SIZE; do
   rocprofv3 --pmc $c --kernel-trace -d $out/pmc_$c -o p --output-format csv -- python bench.py --pmc-child --no-pmc --no-cpu-baseline --no-extra-configs --steps 10 --warmup 2 --chains 1 > /dev/null 2> $out/pmc_$c.err
@@ -29,7 +29,7 @@ python tools/bench_shapes.py 8x3x1024x1024 8x3x768x1024 8x3x768x768 8x3x1024x768
 for s in 8x3x1000x1000 8x3x720x1280; do python tools/prof_shape.py $s; done > $out/generic_planes_kernels.log 2>&1
 python tools/bench_methods.py > $out/bench_methods.log 2>&1
 (python tools/bench_c5.py; python tools/bench_c5.py bf16) > $out/c5_steady_ab.log 2>&1
-DPX_BENCH_FORCE_DIST=1 MASTER_ADDR=127.0.0.1 MASTER_PORT=29533 RANK=0 LOCAL_RANK=0 WORLD_SIZE=1 python bench.py --gpus 1 --steps 20 --warmup 5 --no-extra-configs > $out/bench_forced_dist_path.json 2>> $out/bench.err
+DPX_BENCH_FORCE_DIST=1 MASTER_ADDR=127.0.0.1 MASTER_PORT=29533 RANK=0 LOCAL_RANK=0 WORLD_SIZE=1 python bench.py --full --gpus 1 --steps 20 --warmup 5 --no-extra-configs > $out/bench_forced_dist_path.json 2>> $out/bench.err
 # round 6: Winograd layers against the direct split-f16 ones (accuracy + per-kernel times), the probes behind DESIGN.md sections 9.2 / 9.9
 python tools/bench_wino.py 8 > $out/wino_vs_direct.log 2>&1
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 tools/probe_grid_barrier.hip -o /tmp/probe_grid_barrier.bin && /tmp/probe_grid_barrier.bin > $out/grid_barrier_probe.log 2>&1
