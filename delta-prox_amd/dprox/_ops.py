@@ -1020,3 +1020,23 @@ def cfft2(x, inverse=False, centred=True, ortho=True):
     be.lib().call("dpx_cfft2", ptr(x), ptr(out), int(bool(inverse)), int(bool(centred)), int(bool(ortho)), P, H, W,
                   ptr(fft_table(H, W, x.device)), be.stream())
     return out
+
+
+def nlm(v, sigma, search=11, patch=5):
+    """non-local means of [B, C, H, W] fp32 images (C = 3: the reference's luminance patch distance; C = 1: the plane itself) at the
+    per-image noise level sigma (0-d / [B]): NonLocalMeansFast.forward of the reference in one kernel (dpx_nlm); a new tensor"""
+    if not isinstance(v, torch.Tensor):
+        raise be.DpxError(f"nlm: expected a torch.Tensor, got {type(v)}")
+    if v.is_complex() or v.dtype != torch.float32:
+        raise be.DpxError(f"nlm: expected a real float32 image, got {v.dtype}")
+    B, C, H, W = _shape4(v)
+    if C not in (1, 3):
+        raise be.DpxError(f"nlm: {C} channels (1 or 3)")
+    for name, n, lo, hi in (("search window", search, 3, 21), ("patch", patch, 1, 9)):
+        if int(n) != n or n % 2 != 1 or not lo <= n <= hi:
+            raise be.DpxError(f"nlm: {name} {n} (odd, {lo} .. {hi})")
+    v = require(v.contiguous(), what="nlm input")
+    sig = as_batch_vec(sigma, B, v.device)          # (held until the call returns: a temporary's memory may be reused before the launch)
+    out = torch.empty_like(v)
+    be.lib().call("dpx_nlm", ptr(v), ptr(out), ptr(sig), B, C, H, W, int(search), int(patch), be.stream())
+    return out

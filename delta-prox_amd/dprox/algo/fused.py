@@ -3,7 +3,7 @@
 ``plan_admm`` pattern-matches the compiled problem:
 
     Omega : sum_squares( conv(x, psf) - b )  |  sum_squares( x - b )          (any number)
-    Psi   : norm1 / norm2 / nonneg / deep_prior(FFDNet)  of  x | grad(x, 0) | grad(x, 1)   (<= 4 terms)
+    Psi   : norm1 / norm2 / nonneg / deep_prior(FFDNet) / patch_nlm  of  x | grad(x, 0) | grad(x, 1)   (<= 4 terms; the last two on x)
 
 and replaces the reference's per-iteration graph walks (dprox/algo/admm.py:49-59 ->
 proxfn/sum_square.py:123-156 -> linop/comp_graph.py:198-282; 18 full complex FFTs and ~80 eager ops
@@ -30,7 +30,7 @@ from .. import _ops as ops
 from . import autodiff
 from ..linop import Constant, Variable, conv, conv_doe, grad
 from ..linop import sum as lin_sum
-from ..proxfn import deep_prior, least_squares, nonneg, norm1, norm2, sum_squares
+from ..proxfn import deep_prior, least_squares, nonneg, norm1, norm2, patch_nlm, sum_squares
 from ..proxfn.pnp.denoisers import Denoiser2D, FFDNetColorDenoiser, FFDNetDenoiser
 
 
@@ -86,6 +86,8 @@ def _psi_prox_code(fn):
     if type(fn) is norm2:
         return be.PROX_SUMSQ
     if type(fn) is deep_prior and not fn.unroll and not fn.clamp and isinstance(fn.denoiser, (FFDNetColorDenoiser, FFDNetDenoiser)):
+        return be.PROX_EXTERNAL
+    if type(fn) is patch_nlm:
         return be.PROX_EXTERNAL
     return None
 
@@ -218,15 +220,25 @@ def schedule_table(vals, T, B, device):
     return tab
 
 
+def _lam_table(fn, lt):
+    """[T, B] table an external term's z-update reads: its noise levels (_sigma_table) for a prior, else the lambda schedule itself"""
+    return _sigma_table(fn, lt) if isinstance(fn, (deep_prior, patch_nlm)) else lt
+
+
 def _sigma_table(fn, lt):
     """[T, B] noise levels of a deep_prior term from its lambda schedule: alpha * lam, or safe_sqrt(alpha * lam) with sqrt=True
-    (the scaling of `c * deep_prior(...)` enters before the root: prior.py:77 behind ProxFn.prox, proxfn/base.py:55-64)"""
+    (the scaling of `c * deep_prior(...)` enters before the root: prior.py:77 behind ProxFn.prox, proxfn/base.py:55-64);
+    of a patch_nlm term: sqrt(alpha * lam), unclamped, as patch_nlm._prox takes it behind ProxFn.prox (patch_nlm.py:11)"""
     lt = lt * float(fn.alpha) if float(fn.alpha) != 1.0 else lt
+    if isinstance(fn, patch_nlm):
+        return torch.sqrt(lt)
     return torch.sqrt(torch.clamp(lt, min=1e-8)) if fn.sqrt else lt
 
 
 def _denoise_split(fn, d, sig):
-    """z-update of a deep_prior term: v = D(d; sigma) with d = x + u (the denoiser's own HIP kernels)"""
+    """z-update of a deep_prior / patch_nlm term: v = D(d; sigma) with d = x + u (the denoiser's own HIP kernels; dpx_nlm)"""
+    if isinstance(fn, patch_nlm):
+        return ops.nlm(d, sig, fn.search_window_size, fn.patch_size)
     B, C, H, W = d.shape
     den = fn.denoiser
     if isinstance(den, Denoiser2D):
@@ -287,7 +299,7 @@ class FusedSplitCG:
         lam_tab = []
         for fn in psi:
             lt = schedule_table(lams[fn], T, B, dev)
-            lam_tab.append(_sigma_table(fn, lt) if isinstance(fn, deep_prior) else lt)
+            lam_tab.append(_lam_table(fn, lt))
         v = [t.contiguous() for t in v]
         u = [t.contiguous() for t in u]
         x = x0
@@ -306,7 +318,7 @@ class FusedSplitCG:
         # idle stream per iteration of a 4 x 1 x 320^2 shard.  DPX_SPLIT_CG_STAGED=1: the stage-by-stage loop below (A/B, tests).
         cfg = ls.linear_solve_config
         sysm = ls._masked_fft_system(False) if (cfg.solver_type == "cg" and not cfg.verbose) else None
-        one_call = (len(ext) == 1 and C == 1 and isinstance(psi[ext[0]].denoiser, FFDNetDenoiser) and psi[ext[0]].denoiser.model.in_nc == 1
+        one_call = (len(ext) == 1 and C == 1 and isinstance(getattr(psi[ext[0]], "denoiser", None), FFDNetDenoiser) and psi[ext[0]].denoiser.model.in_nc == 1
                     and not torch.is_grad_enabled() and sysm is not None and B <= 64 and not be.host_mode_skip_fast_cg()
                     and ls._masked_fft_fits(sysm[0], x0) and not os.environ.get("DPX_SPLIT_CG_STAGED"))
         s.last_split_cg_loop = "one call" if one_call else "staged"     # (tests / tools: which loop the last solve took)
@@ -552,7 +564,7 @@ class FusedADMM:
         lam_tab = []
         for fn in (() if want_grad else psi):
             lt = schedule_table(lams[fn], T, B, dev)
-            lam_tab.append(_sigma_table(fn, lt) if isinstance(fn, deep_prior) else lt)     # deep priors: the table holds sigma
+            lam_tab.append(_lam_table(fn, lt))                    # priors: the table holds sigma
         # data spectrum F(sum_Omega K^T b): fp64 transform, kept in the Fourier domain, recomputed only when an
         # offset (the observation b) changes
         _tr("lam tables")
@@ -638,7 +650,7 @@ class FusedADMM:
                                         rhos, lams, pbar, callback, dual, seeded, fresh and seeded is not None)
 
         # one FFDNet prior, everything else closed-form: the whole iteration is ONE C call (dpx_admm_pnp_iter)
-        one_call = (dual and len(ext) == 1 and isinstance(psi[ext[0]].denoiser, (FFDNetColorDenoiser, FFDNetDenoiser))
+        one_call = (dual and len(ext) == 1 and isinstance(getattr(psi[ext[0]], "denoiser", None), (FFDNetColorDenoiser, FFDNetDenoiser))
                     and not torch.is_grad_enabled() and psi[ext[0]].denoiser.model.in_nc in (C, 1))
         if one_call:
             e = ext[0]

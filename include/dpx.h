@@ -694,6 +694,18 @@ size_t dpx_ffdnet_bwd_ws_bytes(int B, int in_nc, int nc, int H, int W);
 int dpx_ffdnet_backward(const float* gy, float* gx, float* gsigma, float* const* gw, float* const* gb, const void* packed_T,
                         const void* acts, int in_nc, int nc, int nb, int B, int H, int W, void* ws, dpx_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------ */
+/* non-local means (patch_nlm prior)                                                           */
+/* ------------------------------------------------------------------------------------------ */
+/* NonLocalMeansFast.forward -- proxfn/nlm/nlm.py:8-27 behind patch_nlm._prox (proxfn/nlm/patch_nlm.py:10-13), one launch:
+ *   out = clamp(sum_s w_s v(p - s) / sum_s w_s, 0, 1),  w_s = exp(-sqrt(D_s) / (relu(2 sigma) + 1e-6)),
+ *   D_s(p) = sum over the patch x patch box around p of (y(q) - y(q - s))^2,  s over the search x search window,
+ * every index circular (torch.roll), y = 0.299 R + 0.587 G + 0.114 B for C = 3 (the reference's luminance) and the plane itself for
+ * C = 1 (an extension: the reference's luminance slicing returns no channel for gray input).  sigma: [B] on the device.  search: odd
+ * 3 .. 21, patch: odd 1 .. 9 (the reference's 11 / 5 have their own kernel).  Any B, H, W >= 1; out must not be v.  The shift stack
+ * is never formed; the shifts are summed in a fixed order (bit-reproducible).                                                  */
+int dpx_nlm(const float* v, float* out, const float* sigma, int B, int C, int H, int W, int search, int patch, dpx_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
