@@ -304,14 +304,9 @@ template <int M, int T, int NT, bool HB>
 static void launch_bwd_rows_hb(const float2* sin, float2* sout, const BwdRowTerms& TT, const float* rho, float* part_a, float* part_b, float* part_lam,
                                int B, int C, int H, int R, int bands, const float2* twW, hipStream_t s) {
   const size_t sh = bwd_rows_lds(M, T);
-  static bool attr = false;
-  if (!attr && sh > 48 * 1024) {
-    hipFuncSetAttribute((const void*)k_bwd_rows<M, T, NT, HB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh);
-    attr = true;
-  }
   const int P = B * C;
-  DPX_LAUNCH("k_bwd_rows", (k_bwd_rows<M, T, NT, HB>), dim3(P * bands), dim3(256), sh, s, sin, sout, TT, rho, part_a, part_b, part_lam, B, C, H, R, bands, P,
-             twW);
+  DPX_LAUNCH_LDS("k_bwd_rows", (k_bwd_rows<M, T, NT, HB>), dim3(P * bands), dim3(256), sh, s, sin, sout, TT, rho, part_a, part_b, part_lam, B, C, H, R, bands,
+                 P, twW);
 }
 template <int M, int T, int NT>
 static void launch_bwd_rows_nt(const float2* sin, float2* sout, const BwdRowTerms& TT, const float* rho, float* part_a, float* part_b, float* part_lam,

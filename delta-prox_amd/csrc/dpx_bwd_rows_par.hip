@@ -360,14 +360,9 @@ static void launch_bp_hb(const float2* sin, float2* sout, const BwdRowTerms& TT,
                          int B, int C, int H, int bands, const float2* twW, hipStream_t s) {
   constexpr int NW = BWD_PAR_NW, G = 64 / T, S = M + M / 16, V = M / T;
   const size_t sh = (size_t)(M + 64 + NW * (G * S + 64 * V + 32)) * sizeof(float2);
-  static bool attr = false;
-  if (!attr) {
-    hipFuncSetAttribute((const void*)k_bwd_rows_par<M, T, NT, HB, NW>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh);
-    attr = true;
-  }
   const int P = B * C;
-  DPX_LAUNCH("k_bwd_rows_par", (k_bwd_rows_par<M, T, NT, HB, NW>), dim3(P * bands), dim3(64 * NW), sh, s, sin, sout, twW, rho, part_a, part_b, part_lam, B,
-             C, H, bands, P, TT);
+  DPX_LAUNCH_LDS("k_bwd_rows_par", (k_bwd_rows_par<M, T, NT, HB, NW>), dim3(P * bands), dim3(64 * NW), sh, s, sin, sout, twW, rho, part_a, part_b, part_lam,
+                 B, C, H, bands, P, TT);
 }
 template <int M, int T, int NT>
 static void launch_bp_nt(const float2* sin, float2* sout, const BwdRowTerms& TT, const float* rho, float* part_a, float* part_b, float* part_lam,

@@ -8,6 +8,7 @@
 #include <hip/hip_ext.h>
 #endif
 
+#include <atomic>
 #include <cstdarg>
 #include <cstdio>
 
@@ -142,6 +143,29 @@ bool timing_events(const char* name, hipEvent_t* start, hipEvent_t* stop);
       hipExtLaunchKernelGGL(kernel, grid, block, shmem, stream, dpx_e0_, dpx_e1_, 0, __VA_ARGS__);         \
     else                                                                                                   \
       hipLaunchKernelGGL(kernel, grid, block, shmem, stream, __VA_ARGS__);                                 \
+  } while (0)
+
+// ---- kernels with more dynamic LDS than a device grants without asking ------------------------------------
+// The one rule of the library ("Launching"): a launch whose dynamic LDS exceeds LDS_NO_OPT_IN goes through
+// DPX_LAUNCH_LDS, which names the kernel instantiation once, opts it in on the CURRENT device
+// (hipFuncAttributeMaxDynamicSharedMemorySize is a per-device function attribute) and remembers the size granted per
+// (call site = kernel instantiation, device): a later launch costs hipGetDevice plus one relaxed atomic load, and asks
+// again only for a larger size.  A refused opt-in is recorded with launch_fail() -- nothing is marked as granted, the
+// kernel is NOT launched, and the C entry point's launch_status() returns DPX_ERR_LAUNCH with that message.
+constexpr size_t LDS_NO_OPT_IN = 48 * 1024;
+constexpr int LDS_GRANT_DEVICES = 32;           // devices with a remembered grant; any beyond them ask on every launch
+struct LdsGrant { std::atomic<int> bytes[LDS_GRANT_DEVICES]; };     // a function-local static: zero-initialised, no guard
+bool lds_opt_in(const char* name, const void* kernel, size_t shmem, LdsGrant& grant);
+// "this launcher could not launch": records the message and a thread-local mark that the next launch_status() of this
+// thread turns into DPX_ERR_LAUNCH (launchers are void; hipGetLastError() knows nothing about a launch that never happened)
+void launch_fail(const char* fmt, ...);
+bool launch_failed();                           // the mark, for a launcher whose next kernel consumes what was not produced
+#define DPX_LAUNCH_LDS(name, kernel, grid, block, shmem, stream, ...)                                                      \
+  do {                                                                                                                     \
+    static ::dpx::LdsGrant dpx_grant_;                                                                                     \
+    const size_t dpx_sh_ = (shmem);                                                                                        \
+    if (dpx_sh_ <= ::dpx::LDS_NO_OPT_IN || ::dpx::lds_opt_in(name, (const void*)kernel, dpx_sh_, dpx_grant_))              \
+      DPX_LAUNCH(name, kernel, grid, block, dpx_sh_, stream, __VA_ARGS__);                                                 \
   } while (0)
 
 #define DPX_REQUIRE(cond, ...)          \

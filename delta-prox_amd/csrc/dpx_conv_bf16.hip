@@ -419,17 +419,9 @@ static void launch_bx_p8(bool relu, bool pre, bool pso, const float* in, float* 
   const int tx = (W + BX_TW - 1) / BX_TW, ty = (H + BX_TH - 1) / BX_TH;
   const size_t sh_pre = (size_t)2 * BX_LAND_BYTES + 2 * bx_slot_bytes(MT, 2), sh_std = (size_t)BX_LAND_BYTES + BX_TILE_BYTES + 2 * bx_slot_bytes(MT, 2);
   const dim3 grid(tx * ty, B);
-#define DPX_BX_P8(R, PRE_, PSO_)                                                                                                             \
-  do {                                                                                                                                       \
-    const size_t sh = PRE_ ? sh_pre : sh_std;                                                                                                \
-    static bool attr = false;                                                                                                                \
-    if (!attr) {                                                                                                                             \
-      hipFuncSetAttribute((const void*)k_conv3x3_bf16<MT, R, 3, PRE_, PSO_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh);           \
-      attr = true;                                                                                                                           \
-    }                                                                                                                                        \
-    DPX_LAUNCH("k_conv3x3_bf16", (k_conv3x3_bf16<MT, R, 3, PRE_, PSO_>), grid, dim3(512), sh, s, in, out, wpk, Gin, Gout, H, W, tx,            \
-               (const float*)nullptr);                                                                                                       \
-  } while (0)
+#define DPX_BX_P8(R, PRE_, PSO_)                                                                                                      \
+  DPX_LAUNCH_LDS("k_conv3x3_bf16", (k_conv3x3_bf16<MT, R, 3, PRE_, PSO_>), grid, dim3(512), PRE_ ? sh_pre : sh_std, s, in, out, wpk, Gin, Gout, H, W, \
+                 tx, (const float*)nullptr)
   if (pre && pso) { if (relu) DPX_BX_P8(true, true, true); else DPX_BX_P8(false, true, true); }
   else if (pre) { if (relu) DPX_BX_P8(true, true, false); else DPX_BX_P8(false, true, false); }
   else if (pso) { if (relu) DPX_BX_P8(true, false, true); else DPX_BX_P8(false, false, true); }
@@ -450,18 +442,12 @@ static void launch_bx_th(bool relu, const float* in, float* out, const char* wpk
   constexpr int NPL = MODE == 1 ? 1 : (MODE == 3 ? 2 : 3), UNITS = 2 * (TH + 2) * BX_COLS;
   const int tx = (W + BX_TW - 1) / BX_TW, ty = (H + TH - 1) / TH;
   const size_t sh = (size_t)((2 * UNITS + 63) / 64) * 1024 + (size_t)(TH == 16 ? 3 : NPL) * UNITS * 16 + 2 * bx_slot_bytes(MT, bx_planes(MODE));
-  static bool attr[2] = {false, false};
-  if (!attr[relu]) {
-    if (relu) hipFuncSetAttribute((const void*)k_conv3x3_bf16<MT, true, MODE, false, false, TH>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh);
-    else hipFuncSetAttribute((const void*)k_conv3x3_bf16<MT, false, MODE, false, false, TH>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh);
-    attr[relu] = true;
-  }
   if (relu)
-    DPX_LAUNCH("k_conv3x3_bf16", (k_conv3x3_bf16<MT, true, MODE, false, false, TH>), dim3(tx * ty, B), dim3(TH * 32), sh, s, in, out, wpk, Gin, Gout, H,
-               W, tx, mask);
+    DPX_LAUNCH_LDS("k_conv3x3_bf16", (k_conv3x3_bf16<MT, true, MODE, false, false, TH>), dim3(tx * ty, B), dim3(TH * 32), sh, s, in, out, wpk, Gin, Gout,
+                   H, W, tx, mask);
   else
-    DPX_LAUNCH("k_conv3x3_bf16", (k_conv3x3_bf16<MT, false, MODE, false, false, TH>), dim3(tx * ty, B), dim3(TH * 32), sh, s, in, out, wpk, Gin, Gout, H,
-               W, tx, mask);
+    DPX_LAUNCH_LDS("k_conv3x3_bf16", (k_conv3x3_bf16<MT, false, MODE, false, false, TH>), dim3(tx * ty, B), dim3(TH * 32), sh, s, in, out, wpk, Gin, Gout,
+                   H, W, tx, mask);
 }
 // knob conv_tile_rows = 8: 8-row tiles (two workgroups per CU) -- measured on the one launch shape they were made for (4 x 1 x 320 x 320:
 // 200 tiles of 16 rows on 256 CUs) they are 2 % SLOWER (a tile is bound by its CU's matrix pipe): off by default
@@ -977,9 +963,17 @@ extern "C" int dpx_ffdnet_backward_bf16_w(const float* gy, float* gx, float* gsi
               "dpx_ffdnet_backward_bf16_w: unsupported configuration (in_nc=%d nc=%d nb=%d mode=%d)", in_nc, nc, nb, mode);
   hipStream_t s = (hipStream_t)stream;
   const int H2 = (H + 1) / 2, W2 = (W + 1) / 2;
-  DPX_REQUIRE((size_t)12 * H2 * W2 * 32 < ((size_t)1 << 32), "dpx_ffdnet_backward_bf16_w: plane %dx%d too large", H, W);
   const size_t px = (size_t)B * H2 * W2;
   const int G0 = groups16(4 * in_nc + 1), Gc = groups16(nc), GL = groups16(4 * in_nc);
+  // every wanted layer must be one k_wgrad_c8 can take (dpx_conv3x3_wgrad_c8's own conditions), before anything is launched
+  for (int l = 0; l < nb; ++l) {
+    if (!gw[l]) continue;
+    const int mt = (bx_cout(l, in_nc, nc, nb) + 31) / 32, nt = (bx_cin(l, in_nc, nc) + 31) / 32, ga = (l == 0) ? G0 : Gc;
+    DPX_REQUIRE(gb[l], "dpx_ffdnet_backward_bf16_w: weight and bias gradients of layer %d come together", l);
+    DPX_REQUIRE(mt <= 3 && nt <= 3 && (mt == nt || mt == 1 || nt == 1),
+                "dpx_ffdnet_backward_bf16_w: layer %d: %d x %d blocks of 32 channels are not instantiated (equal, or one of them 1)", l, mt, nt);
+    DPX_REQUIRE((size_t)ga * H2 * W2 * 32 < ((size_t)1 << 32), "dpx_ffdnet_backward_bf16_w: plane %dx%d too large", H, W);
+  }
   const float* a0 = (const float*)acts;
   const float* hidden = a0 + px * 8 * G0;
   float* g_last = (float*)ws;
@@ -998,7 +992,6 @@ extern "C" int dpx_ffdnet_backward_bf16_w(const float* gy, float* gx, float* gsi
   for (int l = nb - 1; l >= 0; --l) {
     const int cout_f = bx_cout(l, in_nc, nc, nb), cin_f = bx_cin(l, in_nc, nc);     // the FORWARD layer's channel counts
     if (gw[l]) {
-      DPX_REQUIRE(gb[l], "dpx_ffdnet_backward_bf16_w: weight and bias gradients of layer %d come together", l);
       // `cur`: the gradient w.r.t. forward layer l's pre-activation output (the ReLU mask was applied by backward layer l + 1's epilogue)
       const float* a_l = (l == 0) ? a0 : hidden + (size_t)(l - 1) * px * 8 * Gc;
       const int ga = (l == 0) ? G0 : Gc;

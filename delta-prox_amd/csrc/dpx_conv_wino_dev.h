@@ -440,14 +440,8 @@ static void launch_wino(bool relu, const float* in, float* out, const char* wpk,
   }
 #endif
   const int tiles_all = tx * ty * B, nwg = tiles_all < ncu ? tiles_all : ncu;
-  static bool attr[2] = {false, false};
-  if (!attr[relu]) {
-    if (relu) hipFuncSetAttribute((const void*)k_conv3x3_wino<MT, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh);
-    else hipFuncSetAttribute((const void*)k_conv3x3_wino<MT, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh);
-    attr[relu] = true;
-  }
-  if (relu) DPX_LAUNCH("k_conv3x3_wino", (k_conv3x3_wino<MT, true>), dim3(nwg), dim3(512), sh, s, in, out, wpk, Gin, Gout, H, W, tx, tx * ty, tiles_all);
-  else DPX_LAUNCH("k_conv3x3_wino", (k_conv3x3_wino<MT, false>), dim3(nwg), dim3(512), sh, s, in, out, wpk, Gin, Gout, H, W, tx, tx * ty, tiles_all);
+  if (relu) DPX_LAUNCH_LDS("k_conv3x3_wino", (k_conv3x3_wino<MT, true>), dim3(nwg), dim3(512), sh, s, in, out, wpk, Gin, Gout, H, W, tx, tx * ty, tiles_all);
+  else DPX_LAUNCH_LDS("k_conv3x3_wino", (k_conv3x3_wino<MT, false>), dim3(nwg), dim3(512), sh, s, in, out, wpk, Gin, Gout, H, W, tx, tx * ty, tiles_all);
 }
 static void launch_wino_mt(int mt, bool relu, const float* in, float* out, const char* wpk, int Gin, int Gout, int B, int H, int W, hipStream_t s) {
   switch (mt) {

@@ -12,20 +12,60 @@
 namespace dpx {
 static thread_local char g_err[512] = "";
 
+static thread_local bool g_launch_failed = false;   // set by launch_fail(), consumed by launch_status()
+
+// Every error an entry point reports on another way than launch_status() (DPX_REQUIRE, an unsupported size, a failed runtime call: each
+// returns its status right behind set_error) takes the mark with it: an entry that leaves early behind a failed launch cannot hand the
+// mark to the thread's next call.
+static void record_error(bool launch_failed, const char* fmt, va_list ap) {
+  vsnprintf(g_err, sizeof(g_err), fmt, ap);
+  g_launch_failed = launch_failed;
+}
 void set_error(const char* fmt, ...) {
   va_list ap;
   va_start(ap, fmt);
-  vsnprintf(g_err, sizeof(g_err), fmt, ap);
+  record_error(false, fmt, ap);
   va_end(ap);
 }
+void launch_fail(const char* fmt, ...) {
+  va_list ap;
+  va_start(ap, fmt);
+  record_error(true, fmt, ap);
+  va_end(ap);
+}
+bool launch_failed() { return g_launch_failed; }
 
 int launch_status(const char* what) {
   hipError_t e = hipGetLastError();
+  if (g_launch_failed) {                    // a launcher gave up: its message stands, whatever the runtime says
+    g_launch_failed = false;
+    return DPX_ERR_LAUNCH;
+  }
   if (e != hipSuccess) {
     set_error("%s: kernel launch failed: %s", what, hipGetErrorString(e));
     return DPX_ERR_LAUNCH;
   }
   return DPX_OK;
+}
+
+// The opt-in behind DPX_LAUNCH_LDS (dpx_common.h); called only for shmem > LDS_NO_OPT_IN.  The steady state is the relaxed load;
+// the few calls that have to ask are serialised, so that a smaller request of one host thread cannot follow (and undo) a larger
+// one of another whose size is the one remembered.
+bool lds_opt_in(const char* name, const void* kernel, size_t shmem, LdsGrant& grant) {
+  int dev = 0;
+  hipError_t e = hipGetDevice(&dev);
+  std::atomic<int>* slot = e == hipSuccess && dev >= 0 && dev < LDS_GRANT_DEVICES ? &grant.bytes[dev] : nullptr;
+  if (slot && (size_t)slot->load(std::memory_order_relaxed) >= shmem) return true;
+  static std::mutex asking;
+  std::lock_guard<std::mutex> lock(asking);
+  if (slot && (size_t)slot->load(std::memory_order_relaxed) >= shmem) return true;
+  if (e == hipSuccess) e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
+  if (e != hipSuccess) {
+    launch_fail("%s: opt-in to %zu bytes of LDS on device %d failed: %s", name, shmem, dev, hipGetErrorString(e));
+    return false;
+  }
+  if (slot) slot->store((int)shmem, std::memory_order_relaxed);
+  return true;
 }
 }  // namespace dpx
 

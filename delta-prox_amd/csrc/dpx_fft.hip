@@ -1508,9 +1508,6 @@ static int rows_per_block(int M) {
   return r;
 }
 
-template <class K> static void il_lds_attr(K kernel, size_t sh) {
-  if (sh > 48 * 1024) hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh);
-}
 template <bool EVEN, int CT, int NT>
 static void launch_rows_il_t(bool fwd, const float* x, float2* spec, float* y, int W, int nrows, const Plan1D& prow, const float2* twW, hipStream_t s) {
   const size_t sh = (size_t)prow.n * (CT > 1 ? CT + 1 : 1) * sizeof(float2);
@@ -1518,13 +1515,10 @@ static void launch_rows_il_t(bool fwd, const float* x, float2* spec, float* y, i
   // (TWL = false: measured on the one-wave row workgroups, the table copy halves the workgroups a CU holds and costs more than the gathers it
   //  saves -- 8 x 3 x 1000 x 1000: 62.9 -> 68.5 us, 1080 x 1920: 113 -> 170 us; four one-wave rows per workgroup around ONE shared copy were measured too: 64.7 -> 71 us;
   //  the instantiation stays for A/B builds)
-  if (fwd) {
-    il_lds_attr(k_rows_r2c_il<EVEN, CT, NT, false>, sh);
-    DPX_LAUNCH("k_rows_r2c_il", (k_rows_r2c_il<EVEN, CT, NT, false>), grid, dim3(NT), sh, s, x, spec, W, nrows, prow, twW);
-  } else {
-    il_lds_attr(k_rows_c2r_il<EVEN, CT, NT, false>, sh);
-    DPX_LAUNCH("k_rows_c2r_il", (k_rows_c2r_il<EVEN, CT, NT, false>), grid, dim3(NT), sh, s, (const float2*)spec, y, W, nrows, prow, twW, 1.0f);
-  }
+  if (fwd)
+    DPX_LAUNCH_LDS("k_rows_r2c_il", (k_rows_r2c_il<EVEN, CT, NT, false>), grid, dim3(NT), sh, s, x, spec, W, nrows, prow, twW);
+  else
+    DPX_LAUNCH_LDS("k_rows_c2r_il", (k_rows_c2r_il<EVEN, CT, NT, false>), grid, dim3(NT), sh, s, (const float2*)spec, y, W, nrows, prow, twW, 1.0f);
 }
 // ct: 1 = one row per one-wave workgroup (row lengths up to 1024 complex points: the rule), 8 = eight rows interleaved on 512 threads (A/B),
 // 4 = four rows on 512 threads (lengths up to 2048)
@@ -1556,12 +1550,10 @@ static void launch_cols_il_t(float2* spec, const SpecArgs& A, int P, int C, int 
   // the twiddle table in shared memory when the workgroups per CU stay what they are without it (knob il_tw_lds = 0: never)
   const size_t sh_tw = sh + (size_t)H * sizeof(float2), lds_cu = 160 * 1024;
   if (sh_tw <= lds_cu && lds_cu / sh_tw >= (lds_cu / sh > 2 ? 2 : lds_cu / sh)) {
-    il_lds_attr(k_cols_il<OP, CT, NT, true>, sh_tw);
-    DPX_LAUNCH("k_cols_il", (k_cols_il<OP, CT, NT, true>), grid, dim3(NT), sh_tw, s, spec, A, C, H, W, pcol, twH, P);
+    DPX_LAUNCH_LDS("k_cols_il", (k_cols_il<OP, CT, NT, true>), grid, dim3(NT), sh_tw, s, spec, A, C, H, W, pcol, twH, P);
     return;
   }
-  il_lds_attr(k_cols_il<OP, CT, NT, false>, sh);
-  DPX_LAUNCH("k_cols_il", (k_cols_il<OP, CT, NT, false>), grid, dim3(NT), sh, s, spec, A, C, H, W, pcol, twH, P);
+  DPX_LAUNCH_LDS("k_cols_il", (k_cols_il<OP, CT, NT, false>), grid, dim3(NT), sh, s, spec, A, C, H, W, pcol, twH, P);
 }
 template <int CT, int NT>
 static void launch_cols_il_o(int op, float2* spec, const SpecArgs& A, int P, int C, int H, int W, const Plan1D& pcol, const float2* twH, hipStream_t s) {
@@ -1600,9 +1592,9 @@ int spectral_apply(const float* x, float* y, int op, const SpecArgs& A, int B, i
   if (rct) {
     launch_rows_il(true, even, rct, x, spec, y, W, nrows, prow, tw_rows(table), stream);
   } else if (even)
-    DPX_LAUNCH("k_rows_r2c", (k_rows_r2c<true>), grow, dim3(256), shrow, stream, x, spec, W, nrows, prow, tw_rows(table), rpb);
+    DPX_LAUNCH_LDS("k_rows_r2c", (k_rows_r2c<true>), grow, dim3(256), shrow, stream, x, spec, W, nrows, prow, tw_rows(table), rpb);
   else
-    DPX_LAUNCH("k_rows_r2c", (k_rows_r2c<false>), grow, dim3(256), shrow, stream, x, spec, W, nrows, prow, tw_rows(table), rpb);
+    DPX_LAUNCH_LDS("k_rows_r2c", (k_rows_r2c<false>), grow, dim3(256), shrow, stream, x, spec, W, nrows, prow, tw_rows(table), rpb);
   if (cct) launch_cols_il(op, cct, spec, A, P, C, H, W, pcol, tw_cols(table, W), stream);
 
   int CT = (int)(60 * 1024 / (2 * (size_t)(H + 1) * sizeof(float2)));
@@ -1615,22 +1607,18 @@ int spectral_apply(const float* x, float* y, int op, const SpecArgs& A, int B, i
   }
   const dim3 gcol((Ws + CT - 1) / CT, P);
   const float2* twH = tw_cols(table, W);
-  if (shcol > 60 * 1024) {
-    hipFuncSetAttribute((const void*)k_cols<OP_MUL>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shcol);
-    hipFuncSetAttribute((const void*)k_cols<OP_MULCONJ>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shcol);
-    hipFuncSetAttribute((const void*)k_cols<OP_SOLVE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shcol);
-  }
   if (!cct) switch (op) {
-    case OP_MUL: DPX_LAUNCH("k_cols", (k_cols<OP_MUL>), gcol, dim3(256), shcol, stream, spec, A, C, H, W, pcol, twH, CT); break;
-    case OP_MULCONJ: DPX_LAUNCH("k_cols", (k_cols<OP_MULCONJ>), gcol, dim3(256), shcol, stream, spec, A, C, H, W, pcol, twH, CT); break;
-    default: DPX_LAUNCH("k_cols", (k_cols<OP_SOLVE>), gcol, dim3(256), shcol, stream, spec, A, C, H, W, pcol, twH, CT); break;
+    case OP_MUL: DPX_LAUNCH_LDS("k_cols", (k_cols<OP_MUL>), gcol, dim3(256), shcol, stream, spec, A, C, H, W, pcol, twH, CT); break;
+    case OP_MULCONJ: DPX_LAUNCH_LDS("k_cols", (k_cols<OP_MULCONJ>), gcol, dim3(256), shcol, stream, spec, A, C, H, W, pcol, twH, CT); break;
+    default: DPX_LAUNCH_LDS("k_cols", (k_cols<OP_SOLVE>), gcol, dim3(256), shcol, stream, spec, A, C, H, W, pcol, twH, CT); break;
   }
+  if (launch_failed()) return launch_status("spectral_apply");     // y stays as it is rather than receiving half a result
   if (rct)
     launch_rows_il(false, even, rct, x, spec, y, W, nrows, prow, tw_rows(table), stream);
   else if (even)
-    DPX_LAUNCH("k_rows_c2r", (k_rows_c2r<true>), grow, dim3(256), shrow, stream, spec, y, W, nrows, prow, tw_rows(table), rpb, 1.0f);
+    DPX_LAUNCH_LDS("k_rows_c2r", (k_rows_c2r<true>), grow, dim3(256), shrow, stream, spec, y, W, nrows, prow, tw_rows(table), rpb, 1.0f);
   else
-    DPX_LAUNCH("k_rows_c2r", (k_rows_c2r<false>), grow, dim3(256), shrow, stream, spec, y, W, nrows, prow, tw_rows(table), rpb, 1.0f);
+    DPX_LAUNCH_LDS("k_rows_c2r", (k_rows_c2r<false>), grow, dim3(256), shrow, stream, spec, y, W, nrows, prow, tw_rows(table), rpb, 1.0f);
   return launch_status("spectral_apply");
 }
 
@@ -1807,19 +1795,15 @@ extern "C" int dpx_data_spectrum(const float* b, const void* otf, int conj_otf, 
   DPX_LAUNCH("k_twiddle_table_f64", k_twiddle_table_f64, dim3((W + 255) / 256), dim3(256), 0, s, twW, W);
   DPX_LAUNCH("k_twiddle_table_f64", k_twiddle_table_f64, dim3((H + 255) / 256), dim3(256), 0, s, twH, H);
   const int nrows = P * H;
-  if (even) {
-    if (shrow > 48 * 1024) hipFuncSetAttribute((const void*)k_rows_r2c_f64<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shrow);
-    DPX_LAUNCH("k_rows_r2c_f64", k_rows_r2c_f64<true>, dim3((nrows + rpb - 1) / rpb), dim3(env_rt ? env_rt : 256), shrow, s, b, spec64, W, nrows, H, make_plan(M),
-               (const double2*)twW, rpb, CT);
-  } else {
-    if (shrow > 48 * 1024) hipFuncSetAttribute((const void*)k_rows_r2c_f64<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shrow);
-    DPX_LAUNCH("k_rows_r2c_f64", k_rows_r2c_f64<false>, dim3((nrows + rpb - 1) / rpb), dim3(256), shrow, s, b, spec64, W, nrows, H, make_plan(M),
-               (const double2*)twW, rpb, CT);
-  }
-  if (shcol > 48 * 1024) hipFuncSetAttribute((const void*)k_cols_fwd_f64, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shcol);
-  DPX_LAUNCH("k_cols_fwd_f64", k_cols_fwd_f64, dim3((((Wh + CT - 1) / CT + 8 * (16 / CT) - 1) / (8 * (16 / CT))) * (8 * (16 / CT)), P), dim3(env_ct ? env_ct : (CT >= 4 ? 512 : 256)), shcol, s, (const double2*)spec64,
-             (float2*)spec_out, (const float2*)otf, conj_otf, accumulate, C, H, W, make_plan(H),
-             pow2_path_available(H, W) ? 1 : 0, P, (const double2*)twH, CT);
+  if (even)
+    DPX_LAUNCH_LDS("k_rows_r2c_f64", k_rows_r2c_f64<true>, dim3((nrows + rpb - 1) / rpb), dim3(env_rt ? env_rt : 256), shrow, s, b, spec64, W, nrows, H,
+                   make_plan(M), (const double2*)twW, rpb, CT);
+  else
+    DPX_LAUNCH_LDS("k_rows_r2c_f64", k_rows_r2c_f64<false>, dim3((nrows + rpb - 1) / rpb), dim3(256), shrow, s, b, spec64, W, nrows, H, make_plan(M),
+                   (const double2*)twW, rpb, CT);
+  DPX_LAUNCH_LDS("k_cols_fwd_f64", k_cols_fwd_f64, dim3((((Wh + CT - 1) / CT + 8 * (16 / CT) - 1) / (8 * (16 / CT))) * (8 * (16 / CT)), P), dim3(env_ct ? env_ct : (CT >= 4 ? 512 : 256)), shcol, s, (const double2*)spec64,
+                 (float2*)spec_out, (const float2*)otf, conj_otf, accumulate, C, H, W, make_plan(H),
+                 pow2_path_available(H, W) ? 1 : 0, P, (const double2*)twH, CT);
   return launch_status("dpx_data_spectrum");
 }
 

@@ -824,11 +824,6 @@ static void launch_cols(const float2* spec, float2* spec_out, const SpecArgs& A,
   // + the rest of the packed column's H-bin exchange buffer (DPX_COLS_PACK0): 80 KB per workgroup at H = 1024, still two per CU
   constexpr bool TWG = DPX_COLS_TW_GLOBAL && (H >= 2048);      // (cols_body: no LDS copy of the twiddles)
   const size_t sh = (size_t)(COLS * S + (TWG ? 0 : H) + (DPX_COLS_PACK0 && H > COLS * (S - H) ? H - COLS * (S - H) : 0)) * sizeof(float2);
-  static bool attr_done = false;
-  if (!attr_done && sh > 48 * 1024) {
-    hipFuncSetAttribute((const void*)k_cols_p2<H, T, COLS, OP, DBG>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh);
-    attr_done = true;
-  }
   const int total_blocks = P * (Ws / COLS) + (DPX_COLS_PACK0 ? 0 : (P + COLS - 1) / COLS);
   int grid = total_blocks;
 #if DPX_COLS_PERSIST
@@ -837,7 +832,7 @@ static void launch_cols(const float2* spec, float2* spec_out, const SpecArgs& A,
     if (grid > cap) grid = cap;
   }
 #endif
-  DPX_LAUNCH("k_cols_p2", (k_cols_p2<H, T, COLS, OP, DBG>), dim3(grid), dim3(T * COLS), sh, s, spec, spec_out, A, C, Ws, P, twH, total_blocks);
+  DPX_LAUNCH_LDS("k_cols_p2", (k_cols_p2<H, T, COLS, OP, DBG>), dim3(grid), dim3(T * COLS), sh, s, spec, spec_out, A, C, Ws, P, twH, total_blocks);
 }
 
 #ifndef DPX_COLS_WG

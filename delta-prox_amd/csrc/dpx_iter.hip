@@ -259,13 +259,8 @@ template <int M, int T, int NT>
 static void launch_iter_rows_nt(const float2* sin, float2* sout, const IterTerms& TT, const float* rho_next, float* x_out, int emit_v,
                                 int C, int H, int R, int P, const float2* twW, hipStream_t s) {
   const size_t sh = iter_rows_lds(M, T);
-  static bool attr = false;
-  if (!attr && sh > 48 * 1024) {
-    hipFuncSetAttribute((const void*)k_iter_rows<M, T, NT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh);
-    attr = true;
-  }
-  DPX_LAUNCH("k_iter_rows", (k_iter_rows<M, T, NT>), dim3(P * (H / R)), dim3(256), sh, s, sin, sout, TT, rho_next, x_out, emit_v, C,
-             H, R, P, twW);
+  DPX_LAUNCH_LDS("k_iter_rows", (k_iter_rows<M, T, NT>), dim3(P * (H / R)), dim3(256), sh, s, sin, sout, TT, rho_next, x_out, emit_v, C,
+                 H, R, P, twW);
 }
 template <int M, int T>
 static void launch_iter_rows(const float2* sin, float2* sout, const IterTerms& TT, const float* rho_next, float* x_out, int emit_v,
@@ -637,14 +632,9 @@ template <int M, int T, int NT, bool DUAL, bool VXU = false>
 static void launch_iter_rows_seq_d(const float2* sin, float2* sout, const IterTerms& TT, const float* rho_next, float* x_out, int emit_v,
                                    int C, int H, int R, int P, const float2* twW, hipStream_t s) {
   const size_t sh = iter_rows_seq_lds(M, T, DUAL ? NT : 0);
-  static bool attr = false;
-  if (!attr && sh > 48 * 1024) {
-    hipFuncSetAttribute((const void*)k_iter_rows_seq<M, T, NT, DUAL, VXU>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh);
-    attr = true;
-  }
   const int groups = P * R, per_block = 4 * (64 / T);   // R = bands per plane here
-  DPX_LAUNCH(VXU ? "k_iter_rows_seq_vxu" : (DUAL ? "k_iter_rows_seq" : "k_iter_rows_seq_nodual"), (k_iter_rows_seq<M, T, NT, DUAL, VXU>), dim3(groups / per_block),
-             dim3(256), sh, s, sin, sout, TT, rho_next, x_out, emit_v, C, H, R, P, twW);
+  DPX_LAUNCH_LDS(VXU ? "k_iter_rows_seq_vxu" : (DUAL ? "k_iter_rows_seq" : "k_iter_rows_seq_nodual"), (k_iter_rows_seq<M, T, NT, DUAL, VXU>),
+                 dim3(groups / per_block), dim3(256), sh, s, sin, sout, TT, rho_next, x_out, emit_v, C, H, R, P, twW);
 }
 template <int M, int T, int NT>
 static void launch_iter_rows_seq_nt(const float2* sin, float2* sout, const IterTerms& TT, const float* rho_next, float* x_out, int emit_v,
@@ -845,17 +835,11 @@ static bool launch_pgd_rows_seq(const float2* sin, float2* sout, float* x, const
   const int per_block = 4 * G;
   if (nb < 1 || H % nb || (P * nb) % per_block) return false;
   const size_t sh1 = (size_t)(M + 64 + 4 * (G * S + STG + 32 + 1 * STG)) * sizeof(float2), sh2 = (size_t)(M + 64 + 4 * (G * S + STG + 32 + 2 * STG)) * sizeof(float2);
-  static bool attr = false;
-  if (!attr) {
-    hipFuncSetAttribute((const void*)k_pgd_rows_seq<M, T, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh2);
-    hipFuncSetAttribute((const void*)k_pgd_rows_seq<M, T, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh1);
-    attr = true;
-  }
   const dim3 grid(P * nb / per_block);
   if (ktb)
-    DPX_LAUNCH("k_pgd_rows_seq", (k_pgd_rows_seq<M, T, true>), grid, dim3(256), sh2, s, sin, sout, x, ktb, rho, lam, alpha, prox, C, H, nb, P, twW);
+    DPX_LAUNCH_LDS("k_pgd_rows_seq", (k_pgd_rows_seq<M, T, true>), grid, dim3(256), sh2, s, sin, sout, x, ktb, rho, lam, alpha, prox, C, H, nb, P, twW);
   else
-    DPX_LAUNCH("k_pgd_rows_seq", (k_pgd_rows_seq<M, T, false>), grid, dim3(256), sh1, s, sin, sout, x, ktb, rho, lam, alpha, prox, C, H, nb, P, twW);
+    DPX_LAUNCH_LDS("k_pgd_rows_seq", (k_pgd_rows_seq<M, T, false>), grid, dim3(256), sh1, s, sin, sout, x, ktb, rho, lam, alpha, prox, C, H, nb, P, twW);
   return true;
 }
 // false: the plane / batch does not fit the streaming kernel (the caller keeps k_pgd_rows)
@@ -1035,12 +1019,7 @@ static bool launch_seed_rows_seq(const SeedOps& SO, const float* rho, const floa
   const int per_block = 4 * G;
   if (nb < 1 || H % nb || (P * nb) % per_block) return false;
   const size_t sh = (size_t)(M + 64 + 4 * (G * S + 2 * STG)) * sizeof(float2);
-  static bool attr = false;
-  if (!attr && sh > 48 * 1024) {
-    hipFuncSetAttribute((const void*)k_seed_rows_seq<M, T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh);
-    attr = true;
-  }
-  DPX_LAUNCH("k_seed_rows_seq", (k_seed_rows_seq<M, T>), dim3(P * nb / per_block), dim3(256), sh, s, SO, rho, x0, spec, C, H, nb, P, twW);
+  DPX_LAUNCH_LDS("k_seed_rows_seq", (k_seed_rows_seq<M, T>), dim3(P * nb / per_block), dim3(256), sh, s, SO, rho, x0, spec, C, H, nb, P, twW);
   return true;
 }
 // false: the plane / batch does not fit the streaming kernel (the caller keeps k_seed_rows<FRESH>)

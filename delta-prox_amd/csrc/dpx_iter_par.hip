@@ -359,18 +359,11 @@ static void launch_par_d(const float2* sin, float2* sout, const IterTerms& TT, c
   // variables in registers: 8 waves of 256 registers (no scratch in any instantiation: tools/spill_check.py)
   constexpr int NW = (NT >= 3 || VXU) ? 8 : 16, G = 64 / T, S = M + M / 16, V = M / T, RW = NW * G;
   const size_t sh = (size_t)(M + 64 + NW * (G * S + 64 * V + 32)) * sizeof(float2);
-  static unsigned long long attr = 0;                   // one bit per device: the 140 KB opt-in is a per-device function attribute
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  if (!(attr >> (dev & 63) & 1ull)) {
-    hipFuncSetAttribute((const void*)k_iter_rows_par<M, T, NT, DUAL, VXU, NW>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh);
-    attr |= 1ull << (dev & 63);
-  }
   const bool xonly = !DUAL && emit_v == 2;
   const int rows = xonly ? RW : RW - 2;                 // own rows per workgroup
   const int bands = (H + rows - 1) / rows;
-  DPX_LAUNCH(VXU ? "k_iter_rows_par_vxu" : (DUAL ? "k_iter_rows_par" : "k_iter_rows_par_nodual"), (k_iter_rows_par<M, T, NT, DUAL, VXU, NW>),
-             dim3(P * bands), dim3(64 * NW), sh, s, sin, sout, twW, rho_next, x_out, emit_v, C, H, bands, P, TT);
+  DPX_LAUNCH_LDS(VXU ? "k_iter_rows_par_vxu" : (DUAL ? "k_iter_rows_par" : "k_iter_rows_par_nodual"), (k_iter_rows_par<M, T, NT, DUAL, VXU, NW>),
+                 dim3(P * bands), dim3(64 * NW), sh, s, sin, sout, twW, rho_next, x_out, emit_v, C, H, bands, P, TT);
 }
 template <int M, int T, int NT>
 static void launch_par_nt(const float2* sin, float2* sout, const IterTerms& TT, const float* rho_next, float* x_out, int emit_v, int C, int H, int P,

@@ -258,13 +258,8 @@ extern "C" int dpx_psf2otf(const double* psf, int kh, int kw, int kc, int C, int
   if (sh <= 64 * 1024 && !direct) {
     const int Wl = (W % 2 == 0) ? W / 2 + 1 : (W + 1) / 2;
     const long blocks = (long)C * ((H + PT_K - 1) / PT_K) * ((Wl + PT_L - 1) / PT_L);
-    static bool attr = false;
-    if (!attr) {
-      hipFuncSetAttribute((const void*)k_psf2otf_tiled, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
-      attr = true;
-    }
-    DPX_LAUNCH("k_psf2otf_tiled", k_psf2otf_tiled, dim3((unsigned)blocks), dim3(256), sh, (hipStream_t)stream, psf, kh, kw, kc, C, H, W,
-               (float2*)otf, (float*)diag, weight, accumulate, pow2_path_available(H, W) ? 1 : 0);
+    DPX_LAUNCH_LDS("k_psf2otf_tiled", k_psf2otf_tiled, dim3((unsigned)blocks), dim3(256), sh, (hipStream_t)stream, psf, kh, kw, kc, C, H, W,
+                   (float2*)otf, (float*)diag, weight, accumulate, pow2_path_available(H, W) ? 1 : 0);
     return launch_status("dpx_psf2otf");
   }
   DPX_LAUNCH("k_psf2otf", k_psf2otf, dim3(grid_for(total, 256, 4096)), dim3(256), 0, (hipStream_t)stream, psf, kh, kw, kc, C, H,

@@ -60,15 +60,8 @@ template <int MT, int NT, int MODE>
 static void launch_wc(const float* G, const float* A, float* part, float* part_b, int Gg, int Ga, int B, int H, int W, int nstrips, long nchunks,
                       int NG, hipStream_t s) {
   typedef WcGeom<MT, NT, MODE> GM;
-  static unsigned long long attr = 0;                   // one bit per device: the opt-in beyond 64 KB is a per-device function attribute
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  if (!(attr >> (dev & 63) & 1ull)) {
-    hipFuncSetAttribute((const void*)k_wgrad_c8<MT, NT, MODE>, hipFuncAttributeMaxDynamicSharedMemorySize, GM::LDS_BYTES);
-    attr |= 1ull << (dev & 63);
-  }
-  DPX_LAUNCH("k_wgrad_c8", (k_wgrad_c8<MT, NT, MODE>), dim3(NG), dim3(WC_NW * 64), GM::LDS_BYTES, s, G, A, part, part_b, Gg, Ga, B, H, W, nstrips,
-             nchunks, f16_overflow_flag());
+  DPX_LAUNCH_LDS("k_wgrad_c8", (k_wgrad_c8<MT, NT, MODE>), dim3(NG), dim3(WC_NW * 64), GM::LDS_BYTES, s, G, A, part, part_b, Gg, Ga, B, H, W, nstrips,
+                 nchunks, f16_overflow_flag());
 }
 // the shapes an FFDNet stack has: first layer (MT, 1), hidden layers (MT, MT), last layer (1, NT)
 template <int MODE>
@@ -83,7 +76,7 @@ static void launch_wc_mt(int mt, int nt, const float* G, const float* A, float* 
     case 10: DPX_WC(2, 2); break;
     case 13: DPX_WC(3, 1); break;
     case 15: DPX_WC(3, 3); break;
-    default: set_error("k_wgrad_c8: no instantiation for %d x %d channel blocks", mt, nt); break;
+    default: launch_fail("k_wgrad_c8: no instantiation for %d x %d channel blocks", mt, nt); break;
   }
 #undef DPX_WC
 }
@@ -101,6 +94,7 @@ void launch_wgrad_c8(int mode, const float* G, const float* A, float* gw, float*
   float* part_b = ws + (size_t)NG * CoP * CiP * 9;
   if (mode == 3) launch_wc_mt<3>(MT, NT, G, A, part, part_b, Gg, Ga, B, H, W, nstrips, nchunks, NG, s);
   else launch_wc_mt<6>(MT, NT, G, A, part, part_b, Gg, Ga, B, H, W, nstrips, nchunks, NG, s);
+  if (launch_failed()) return;                          // no partial sums to reduce: the C entry's launch_status() reports why
   DPX_LAUNCH("k_wgrad_c8_reduce", k_wgrad_c8_reduce, dim3(grid_for((long)CoP * CiP * 9, 256, 1024)), dim3(256), 0, s, (const float*)part,
              (const float*)part_b, gw, gb, NG, Cout, Cin_w, MT, NT, mul);
 }

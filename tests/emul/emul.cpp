@@ -6,6 +6,8 @@
 #include <sys/mman.h>
 #include <ucontext.h>
 
+#include <map>
+#include <utility>
 #include <vector>
 
 namespace emul {
@@ -118,9 +120,28 @@ static void run_block(unsigned nthreads) {
   }
 }
 
-void launch(const std::function<void()>& body, dim3 grid, dim3 block, size_t shmem) {
+// ---- the opt-in to large dynamic LDS (hipFuncSetAttribute) ---------------------------------------------------
+struct LdsCall { const void* kernel; int device, bytes; };
+static std::vector<LdsCall> g_lds_log;                       // every call, granted or refused, in order
+static std::map<std::pair<const void*, int>, int> g_lds_granted;   // (kernel, device) -> bytes of the last granted call
+static int g_device = 0, g_lds_limit = -1, g_lds_unasked = 0;
+static constexpr size_t LDS_WITHOUT_ASKING = 64 * 1024;      // what a launch gets on the real runtime with no opt-in
+
+int current_device() { return g_device; }
+int func_set_max_dynamic_lds(const void* kernel, int bytes) {
+  g_lds_log.push_back({kernel, g_device, bytes});
+  if (g_lds_limit >= 0 && bytes > g_lds_limit) return hipErrorInvalidValue;
+  g_lds_granted[{kernel, g_device}] = bytes;
+  return hipSuccess;
+}
+
+void launch(const std::function<void()>& body, dim3 grid, dim3 block, size_t shmem, const void* kernel) {
   unsigned nthreads = block.x * block.y * block.z;
   if (nthreads == 0 || nthreads > 1024) { fprintf(stderr, "emul: bad block size %u\n", nthreads); abort(); }
+  if (shmem > LDS_WITHOUT_ASKING) {                          // counted, not fatal: a test reads emul_lds_unasked()
+    auto it = g_lds_granted.find({kernel, g_device});
+    if (it == g_lds_granted.end() || (size_t)it->second < shmem) ++g_lds_unasked;
+  }
   while (pool.size() < nthreads) {
     Fiber* f = new Fiber();
     f->stack = (char*)mmap(nullptr, STACK, PROT_READ | PROT_WRITE, MAP_PRIVATE | MAP_ANONYMOUS | MAP_NORESERVE, -1, 0);
@@ -141,3 +162,19 @@ void launch(const std::function<void()>& body, dim3 grid, dim3 block, size_t shm
   body_fn = nullptr;
 }
 }  // namespace emul
+
+// ---- controls for the tests of the launch layer (ctypes) -----------------------------------------------------
+extern "C" void emul_set_device(int d) { emul::g_device = d; }
+extern "C" void emul_lds_limit(int bytes) { emul::g_lds_limit = bytes; }        // refuse requests above it; < 0: grant everything
+extern "C" void emul_lds_log_clear() { emul::g_lds_log.clear(); }
+extern "C" int emul_lds_unasked() { return emul::g_lds_unasked; }                // launches beyond 64 KB of LDS that held no grant
+// copies up to cap calls; returns how many were recorded
+extern "C" int emul_lds_log(const void** kernel, int* device, int* bytes, int cap) {
+  const int n = (int)emul::g_lds_log.size();
+  for (int i = 0; i < n && i < cap; ++i) {
+    kernel[i] = emul::g_lds_log[i].kernel;
+    device[i] = emul::g_lds_log[i].device;
+    bytes[i] = emul::g_lds_log[i].bytes;
+  }
+  return n;
+}

@@ -69,7 +69,11 @@ const Idx& bid();
 const Idx& bdim();
 const Idx& gdim();
 int lane();
-void launch(const std::function<void()>& body, dim3 grid, dim3 block, size_t shmem);
+void launch(const std::function<void()>& body, dim3 grid, dim3 block, size_t shmem, const void* kernel);
+// the opt-in to large dynamic LDS: recorded per call (kernel, current device, bytes), refusable above a limit, and checked at
+// launch -- see the emul_* controls at the end of emul.cpp
+int func_set_max_dynamic_lds(const void* kernel, int bytes);
+int current_device();
 void sync_block();
 void sync_wave();
 char* dyn_smem();
@@ -271,11 +275,12 @@ static inline float __fdividef(float a, float b) { return a / b; }
 static inline float __frcp_rn(float a) { return 1.0f / a; }
 
 #define hipLaunchKernelGGL(kernel, grid, block, shmem, stream, ...) \
-  ::emul::launch([=]() { kernel(__VA_ARGS__); }, dim3(grid), dim3(block), (size_t)(shmem))
+  ::emul::launch([=]() { kernel(__VA_ARGS__); }, dim3(grid), dim3(block), (size_t)(shmem), (const void*)kernel)
 
 // ---- misc runtime shims ---------------------------------------------------------------------------
 #define hipFuncAttributeMaxDynamicSharedMemorySize 8
-static inline hipError_t hipFuncSetAttribute(const void*, int, int) { return 0; }
+#define hipErrorInvalidValue 1
+static inline hipError_t hipFuncSetAttribute(const void* kernel, int, int bytes) { return ::emul::func_set_max_dynamic_lds(kernel, bytes); }
 static inline int __mul24(int a, int b) { return a * b; }
 template <class T> static inline T min(T a, T b) { return a < b ? a : b; }
 template <class T> static inline T max(T a, T b) { return a > b ? a : b; }
@@ -300,6 +305,6 @@ static inline hipError_t hipEventSynchronize(hipEvent_t) { return 0; }
 static inline hipError_t hipStreamSynchronize(hipStream_t) { return 0; }
 static inline hipError_t hipEventElapsedTime(float* ms, hipEvent_t, hipEvent_t) { *ms = 0.f; return 0; }
 static inline hipError_t hipEventDestroy(hipEvent_t) { return 0; }
-static inline hipError_t hipGetDevice(int* d) { *d = 0; return 0; }
+static inline hipError_t hipGetDevice(int* d) { *d = ::emul::current_device(); return 0; }
 static inline hipError_t hipHostFree(void* p) { free(p); return 0; }
 static inline hipError_t hipHostGetDevicePointer(void** d, void* h, unsigned) { *d = h; return 0; }
