@@ -24,6 +24,7 @@
 #endif
 #include "dpx_fft_reg.h"
 #include "dpx_bwd_dev.h"
+#include "dpx_dispatch.h"
 
 namespace dpx {
 
@@ -35,7 +36,8 @@ __global__ void __launch_bounds__(256, (NT >= 3 || (NT == 2 && !HB)) ? 1 : 2) k_
                                                    const float* __restrict__ rho_b, float* __restrict__ part_a, float* __restrict__ part_b,
                                                    float* __restrict__ part_lam, int B, int C, int H, int R, int bands, int P,
                                                    const float2* __restrict__ twW) {
-  constexpr int V = M / T, SPB = 256 / T, S = LdsSeq<M>::SLOTS, RING = SPB + 2;     // (row qz - 1 = q - 2 is read while row q + SPB - 1 arrives)
+  using L = BwdRowsLds<M, T>;                                                    // (row qz - 1 = q - 2 is read while row q + SPB - 1 arrives)
+  constexpr int V = M / T, SPB = L::SPB, S = L::S, RING = L::RING;
   HIP_DYNAMIC_SHARED(float2, smem_bw)
   __shared__ float red[4 * (2 + DPX_MAX_TERMS)];
   float2* fft_lds = smem_bw;                          // SPB * S
@@ -295,39 +297,11 @@ __global__ void __launch_bounds__(256, (NT >= 3 || (NT == 2 && !HB)) ? 1 : 2) k_
   }
 }
 
-static size_t bwd_rows_lds(int M, int T) {
-  const int SPB = 256 / T, S = M + M / 16;
-  return (size_t)(SPB * S + 2 * (SPB + 2) * M) * sizeof(float2);
-}
-
-template <int M, int T, int NT, bool HB>
-static void launch_bwd_rows_hb(const float2* sin, float2* sout, const BwdRowTerms& TT, const float* rho, float* part_a, float* part_b, float* part_lam,
-                               int B, int C, int H, int R, int bands, const float2* twW, hipStream_t s) {
-  const size_t sh = bwd_rows_lds(M, T);
-  const int P = B * C;
-  DPX_LAUNCH_LDS("k_bwd_rows", (k_bwd_rows<M, T, NT, HB>), dim3(P * bands), dim3(256), sh, s, sin, sout, TT, rho, part_a, part_b, part_lam, B, C, H, R, bands,
-                 P, twW);
-}
-template <int M, int T, int NT>
-static void launch_bwd_rows_nt(const float2* sin, float2* sout, const BwdRowTerms& TT, const float* rho, float* part_a, float* part_b, float* part_lam,
-                               int B, int C, int H, int R, int bands, const float2* twW, hipStream_t s) {
-  if (TT.hist_bf16) launch_bwd_rows_hb<M, T, NT, true>(sin, sout, TT, rho, part_a, part_b, part_lam, B, C, H, R, bands, twW, s);
-  else launch_bwd_rows_hb<M, T, NT, false>(sin, sout, TT, rho, part_a, part_b, part_lam, B, C, H, R, bands, twW, s);
-}
-template <int M, int T>
-static void launch_bwd_rows(const float2* sin, float2* sout, const BwdRowTerms& TT, const float* rho, float* part_a, float* part_b, float* part_lam,
-                            int B, int C, int H, int R, int bands, const float2* twW, hipStream_t s) {
-  switch (TT.n) {
-    case 1: launch_bwd_rows_nt<M, T, 1>(sin, sout, TT, rho, part_a, part_b, part_lam, B, C, H, R, bands, twW, s); break;
-    case 2: launch_bwd_rows_nt<M, T, 2>(sin, sout, TT, rho, part_a, part_b, part_lam, B, C, H, R, bands, twW, s); break;
-    case 3: launch_bwd_rows_nt<M, T, 3>(sin, sout, TT, rho, part_a, part_b, part_lam, B, C, H, R, bands, twW, s); break;
-    default: launch_bwd_rows_nt<M, T, 4>(sin, sout, TT, rho, part_a, part_b, part_lam, B, C, H, R, bands, twW, s); break;
-  }
-}
-
 // rows per band: two lock-step rounds of the workgroup's SPB row sequences (2 SPB - 2 rows + the two halo rows); knob unroll_bwd_band
 static int bwd_rows_band(int H, int W) {
-  const int SPB = 256 / (W / 16);
+  const int T = rows_wave_lanes(W);
+  if (!T) return 0;                                      // (a width without row kernel: bwd_rows_slots answers 0, bwd_rows_fused refuses)
+  const int SPB = 256 / T;
   int R = tune(TUNE_UNROLL_BWD_BAND);
   if (R <= 0) R = 2 * SPB - 2;
   if (R < 2) R = 2;
@@ -360,12 +334,23 @@ int bwd_rows_fused(const void* spec_in, void* spec_out, const float* x, const fl
   const float2* tw = tw_rows(table);
   if (const int own = bwd_rows_par_own(B * C, H, W))
     return bwd_rows_par_launch((const float2*)spec_in, (float2*)spec_out, TT, rho, part_a, part_b, part_lam, B, C, H, W, (H + own - 1) / own, tw, s);
-  const int R = bwd_rows_band(H, W), bands = (H + R - 1) / R;
-  switch (W) {
-    case 256: launch_bwd_rows<128, 16>((const float2*)spec_in, (float2*)spec_out, TT, rho, part_a, part_b, part_lam, B, C, H, R, bands, tw, s); break;
-    case 512: launch_bwd_rows<256, 32>((const float2*)spec_in, (float2*)spec_out, TT, rho, part_a, part_b, part_lam, B, C, H, R, bands, tw, s); break;
-    default: launch_bwd_rows<512, 64>((const float2*)spec_in, (float2*)spec_out, TT, rho, part_a, part_b, part_lam, B, C, H, R, bands, tw, s); break;
-  }
+  const int R = bwd_rows_band(H, W);
+  DPX_REQUIRE(R > 0, "dpx_admm_unrolled_backward: no row kernel for %d-wide planes", W);
+  const int bands = (H + R - 1) / R, P = B * C;
+  const bool launched = dispatch_rows_plain(W, [&](auto shape) {
+    constexpr int M = decltype(shape)::M, T = decltype(shape)::T;
+    if constexpr (M != 8 * T) return false;                // (eight values per lane: 256, 512, 1024 -- bwd_rows_slots' widths)
+    else {
+      dispatch_nterms(TT.n, [&](auto nt) {
+        dispatch_flag(TT.hist_bf16 != 0, [&](auto hb) {
+          DPX_LAUNCH_LDS("k_bwd_rows", (k_bwd_rows<M, T, decltype(nt)::value, decltype(hb)::value>), dim3(P * bands), dim3(256), (BwdRowsLds<M, T>::BYTES),
+                         s, (const float2*)spec_in, (float2*)spec_out, TT, rho, part_a, part_b, part_lam, B, C, H, R, bands, P, tw);
+        });
+      });
+      return true;
+    }
+  });
+  if (!launched) launch_fail("k_bwd_rows: no instantiation for %d-wide planes", W);
   return launch_status("dpx_admm_unrolled_backward");
 }
 

@@ -14,6 +14,7 @@
 #define DPX_FFT_BASEOFF 1
 #endif
 #include "dpx_bwd_dev.h"
+#include "dpx_dispatch.h"
 
 namespace dpx {
 
@@ -28,17 +29,18 @@ __global__ void __launch_bounds__(64 * NW, 4) k_bwd_rows_par(const float2* __res
                                                             float* __restrict__ part_a, float* __restrict__ part_b, float* __restrict__ part_lam,
                                                             int B, int C, int H, int bands, int P, BwdRowTerms TT) {
   constexpr int V = M / T, G = 64 / T, S = LdsSeq<M>::SLOTS, D = V / 2, RM = M / (V * V);
-  constexpr int STG = 64 * V, PERWAVE = G * S + STG + 32, RW = NW * G;
+  using L = RowsParLds<M, T, NW>;
+  constexpr int STG = 64 * V, PERWAVE = L::PERWAVE, RW = NW * G;
   static_assert(V == 8 && STG + 32 == G * S, "row-parallel geometry");
   HIP_DYNAMIC_SHARED(float2, smem_bp)
   __shared__ double red[NW * (2 + DPX_MAX_TERMS)];
   float2* twl = smem_bp;
   float2* twb = smem_bp + M;
-  float2* waves = twb + 64;
+  float2* waves = twl + L::WAVES;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int g = lane / T, t = lane % T, lbase = lane & ~(T - 1);
-  float2* wl = waves + wave * PERWAVE;
+  float2* wl = waves + wave * L::PERWAVE;
   float2* myfft = wl + g * S;                           // inverse transform's scratch; then g_d of the grad_H term for the row below
   float2* stX = wl + G * S;                             // DMA staging; then g of this wave's rows; then the forward transform's scratch
   float* stN = (float*)(stX + STG);
@@ -355,48 +357,33 @@ __global__ void __launch_bounds__(64 * NW, 4) k_bwd_rows_par(const float2* __res
 #endif
 constexpr int BWD_PAR_NW = DPX_BWD_PAR_NW;
 
-template <int M, int T, int NT, bool HB>
-static void launch_bp_hb(const float2* sin, float2* sout, const BwdRowTerms& TT, const float* rho, float* part_a, float* part_b, float* part_lam,
-                         int B, int C, int H, int bands, const float2* twW, hipStream_t s) {
-  constexpr int NW = BWD_PAR_NW, G = 64 / T, S = M + M / 16, V = M / T;
-  const size_t sh = (size_t)(M + 64 + NW * (G * S + 64 * V + 32)) * sizeof(float2);
-  const int P = B * C;
-  DPX_LAUNCH_LDS("k_bwd_rows_par", (k_bwd_rows_par<M, T, NT, HB, NW>), dim3(P * bands), dim3(64 * NW), sh, s, sin, sout, twW, rho, part_a, part_b, part_lam,
-                 B, C, H, bands, P, TT);
-}
-template <int M, int T, int NT>
-static void launch_bp_nt(const float2* sin, float2* sout, const BwdRowTerms& TT, const float* rho, float* part_a, float* part_b, float* part_lam,
-                         int B, int C, int H, int bands, const float2* twW, hipStream_t s) {
-  if (TT.hist_bf16) launch_bp_hb<M, T, NT, true>(sin, sout, TT, rho, part_a, part_b, part_lam, B, C, H, bands, twW, s);
-  else launch_bp_hb<M, T, NT, false>(sin, sout, TT, rho, part_a, part_b, part_lam, B, C, H, bands, twW, s);
-}
-template <int M, int T>
-static void launch_bp(const float2* sin, float2* sout, const BwdRowTerms& TT, const float* rho, float* part_a, float* part_b, float* part_lam,
-                      int B, int C, int H, int bands, const float2* twW, hipStream_t s) {
-  switch (TT.n) {
-    case 1: launch_bp_nt<M, T, 1>(sin, sout, TT, rho, part_a, part_b, part_lam, B, C, H, bands, twW, s); break;
-    case 2: launch_bp_nt<M, T, 2>(sin, sout, TT, rho, part_a, part_b, part_lam, B, C, H, bands, twW, s); break;
-    case 3: launch_bp_nt<M, T, 3>(sin, sout, TT, rho, part_a, part_b, part_lam, B, C, H, bands, twW, s); break;
-    default: launch_bp_nt<M, T, 4>(sin, sout, TT, rho, part_a, part_b, part_lam, B, C, H, bands, twW, s); break;
-  }
-}
-
 // own rows per workgroup (0: the lock-step kernel keeps the launch): launches of up to `unroll_bwd_par_max_rows` rows (planes x H; the
 // library's rule: 12288 -- config 5's twelve 512-row planes in one round of 16-wave workgroups), knob < 0 = never
 int bwd_rows_par_own(int P, int H, int W) {
-  if (!(W == 256 || W == 512 || W == 1024)) return 0;
+  if (!(W == 256 || W == 512 || W == 1024)) return 0;      // (so rows_wave_lanes(W) below is 16, 32 or 64)
   const int knob = tune(TUNE_UNROLL_BWD_PAR_MAX_ROWS);
   const long max_rows = knob > 0 ? knob : (knob < 0 ? 0 : 12288);
   if ((long)P * H > max_rows) return 0;
-  return BWD_PAR_NW * (64 / (W / 16)) - 2;
+  return BWD_PAR_NW * (64 / rows_wave_lanes(W)) - 2;
 }
 int bwd_rows_par_launch(const float2* sin, float2* sout, const BwdRowTerms& TT, const float* rho, float* part_a, float* part_b, float* part_lam, int B,
                         int C, int H, int W, int bands, const float2* twW, hipStream_t s) {
-  switch (W) {
-    case 256: launch_bp<128, 16>(sin, sout, TT, rho, part_a, part_b, part_lam, B, C, H, bands, twW, s); break;
-    case 512: launch_bp<256, 32>(sin, sout, TT, rho, part_a, part_b, part_lam, B, C, H, bands, twW, s); break;
-    default: launch_bp<512, 64>(sin, sout, TT, rho, part_a, part_b, part_lam, B, C, H, bands, twW, s); break;
-  }
+  const int P = B * C;
+  const bool launched = dispatch_rows_wave(W, [&](auto shape) {
+    constexpr int M = decltype(shape)::M, T = decltype(shape)::T;
+    if constexpr (M != 8 * T) return false;                // (eight values per lane: 256, 512, 1024 -- bwd_rows_par_own's widths)
+    else {
+      dispatch_nterms(TT.n, [&](auto nt) {
+        dispatch_flag(TT.hist_bf16 != 0, [&](auto hb) {
+          constexpr int NT = decltype(nt)::value, NW = BWD_PAR_NW;
+          DPX_LAUNCH_LDS("k_bwd_rows_par", (k_bwd_rows_par<M, T, NT, decltype(hb)::value, NW>), dim3(P * bands), dim3(64 * NW),
+                         (RowsParLds<M, T, NW>::BYTES), s, sin, sout, twW, rho, part_a, part_b, part_lam, B, C, H, bands, P, TT);
+        });
+      });
+      return true;
+    }
+  });
+  if (!launched) launch_fail("k_bwd_rows_par: no instantiation for %d-wide planes", W);
   return launch_status("dpx_admm_unrolled_backward");
 }
 

@@ -1126,7 +1126,6 @@ namespace dpx {
 // x / p / Ap non-null: the pending update x += alpha p, r -= alpha A p of the previous iteration is applied on the way (r is written)
 int gram_test_fused(float* r, float* G, void* state, int B, long n_per_batch, void* ws, unsigned* counter, float init_rtol, float* x, const float* p,
                     const float* Ap, int* host_flags, int host_tag, hipStream_t s) {
-  const int env_blk = 0;                              // (0 = by size)
   int nblk = gram_blocks(n_per_batch);
   // the finishing workgroup adds up B * B * nblk partial products: for larger batches fewer, longer slab walks (B = 32: 64 workgroups)
   if (B > 8) {
@@ -1134,12 +1133,10 @@ int gram_test_fused(float* r, float* G, void* state, int B, long n_per_batch, vo
     cap = cap < 32 ? 32 : cap;
     if (nblk > cap) nblk = cap;
   }
-  if (env_blk > 0 && env_blk < nblk) nblk = env_blk;
   const bool al16 = ((size_t)r % 16 == 0) && (!x || (((size_t)x % 16 == 0) && ((size_t)p % 16 == 0) && ((size_t)Ap % 16 == 0)));
   if (B <= 8 && n_per_batch % 4 == 0 && al16 && tune(TUNE_CG_GRAM_SMALL) != 2) {
     int nb = (int)((n_per_batch / 4 + 255) / 256);
     nb = nb > 256 ? 256 : (nb < 1 ? 1 : nb);
-    if (env_blk > 0 && env_blk < nb) nb = env_blk;
     const CgState S{(float*)state, B};
 #define DPX_GRAM_SMALL(BT)                                                                                                                       \
   do {                                                                                                                                           \

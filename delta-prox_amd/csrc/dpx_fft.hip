@@ -1753,9 +1753,7 @@ extern "C" int dpx_fft_conv(const float* x, float* y, const void* otf, int conj_
 static size_t ds_ld(int n) { return (size_t)n + n / 8 + 1; }      // padded LDS length of one fp64 sequence (IdxPad8)
 static int ds_ct(int H) {
   // two columns per workgroup (256 threads, two workgroups per CU: one loads while the other transforms) beat four (512 threads, one per
-  // CU) at 8x3x1024^2: column pass 234 vs 267 us, row pass 164 vs 156 us (64-byte instead of 128-byte pieces); DPX_DS_CT=4 forces four
-  const int env = 0;
-  if (env == 4 && 4 * 2 * ds_ld(H) * sizeof(double2) <= 160 * 1024) return 4;
+  // CU) at 8x3x1024^2: column pass 234 vs 267 us, row pass 164 vs 156 us (64-byte instead of 128-byte pieces)
   return 2 * 2 * ds_ld(H) * sizeof(double2) <= 160 * 1024 ? 2 : 0;
 }
 static int ds_rpb(int W) {

@@ -11,6 +11,7 @@
 //   k_rows_c2r_p2 : inverse of the first.
 // Every element crosses HBM once per kernel (8 B/element algorithmic traffic each) and LDS twice per 1-D
 // transform.
+#include "dpx_dispatch.h"
 #include "dpx_fft_reg.h"
 
 #include <cstdlib>
@@ -795,26 +796,19 @@ bool pow2_path_available(int H, int W) {
   return hok && wok;
 }
 
-template <int M, int T>
-static void launch_rows(bool fwd, const float* x, float2* spec, float* y, int nrows, int H, const float2* twW, float scale, hipStream_t s) {
-  constexpr int SPB = 256 / T;
-  const dim3 grid((nrows + SPB - 1) / SPB);
-  float2* side = spec + (size_t)nrows * M;           // [P][H] Nyquist bins behind the main [P][H][W/2] array
-  if (fwd)
-    DPX_LAUNCH("k_rows_r2c_p2", (k_rows_r2c_p2<M, T>), grid, dim3(256), 0, s, x, spec, side, nrows, H, twW);
-  else
-    DPX_LAUNCH("k_rows_c2r_p2", (k_rows_c2r_p2<M, T>), grid, dim3(256), 0, s, (const float2*)spec, (const float2*)side, y, nrows, H, twW, scale);
-}
-
+// (every width of pow2_path_available is in the plain map)
 static void rows_dispatch(bool fwd, int W, int H, const float* x, float2* spec, float* y, int nrows, const float2* twW, float scale, hipStream_t s) {
-  switch (W) {
-    case 256: launch_rows<128, 16>(fwd, x, spec, y, nrows, H, twW, scale, s); break;
-    case 512: launch_rows<256, 32>(fwd, x, spec, y, nrows, H, twW, scale, s); break;
-    case 768: launch_rows<384, 16>(fwd, x, spec, y, nrows, H, twW, scale, s); break;
-    case 1536: launch_rows<768, 32>(fwd, x, spec, y, nrows, H, twW, scale, s); break;
-    case 1024: launch_rows<512, 64>(fwd, x, spec, y, nrows, H, twW, scale, s); break;
-    default: launch_rows<1024, 64>(fwd, x, spec, y, nrows, H, twW, scale, s); break;
-  }
+  const bool launched = dispatch_rows_plain(W, [&](auto shape) {
+    constexpr int M = decltype(shape)::M, T = decltype(shape)::T, SPB = 256 / T;
+    const dim3 grid((nrows + SPB - 1) / SPB);
+    float2* side = spec + (size_t)nrows * M;           // [P][H] Nyquist bins behind the main [P][H][W/2] array
+    if (fwd)
+      DPX_LAUNCH("k_rows_r2c_p2", (k_rows_r2c_p2<M, T>), grid, dim3(256), 0, s, x, spec, side, nrows, H, twW);
+    else
+      DPX_LAUNCH("k_rows_c2r_p2", (k_rows_c2r_p2<M, T>), grid, dim3(256), 0, s, (const float2*)spec, (const float2*)side, y, nrows, H, twW, scale);
+    return true;
+  });
+  if (!launched) launch_fail("k_rows_%s_p2: no instantiation for %d-wide rows", fwd ? "r2c" : "c2r", W);
 }
 
 template <int H, int T, int COLS, int OP, int DBG = 0>
@@ -857,16 +851,6 @@ static void cols_dispatch(int H, const float2* spec, float2* spec_out, const Spe
 
 bool seed_rows_seq_pow2(const int* linops, int n, const float* rho, const float* x0, float2* spec, int P, int C, int H, int W, const void* table,
                         hipStream_t s);
-template <int M, int T>
-static void launch_seed(const SeedTerms& S_, const float* rho, float2* spec, int nrows, int H, int C, const float2* twW, hipStream_t s) {
-  constexpr int SPB = 256 / T;
-  if (S_.x0)
-    DPX_LAUNCH("k_seed_rows", (k_seed_rows<M, T, true>), dim3((nrows + SPB - 1) / SPB), dim3(256), 0, s, S_, rho, spec, spec + (size_t)nrows * M, nrows, H,
-               C, twW);
-  else
-    DPX_LAUNCH("k_seed_rows", (k_seed_rows<M, T, false>), dim3((nrows + SPB - 1) / SPB), dim3(256), 0, s, S_, rho, spec, spec + (size_t)nrows * M, nrows, H,
-               C, twW);
-}
 int seed_rows_pow2(const dpx_term* terms, int nterms, const float* rho, const float* x0, float2* spec, int B, int C, int H, int W, const void* table,
                    hipStream_t stream) {
   SeedTerms S_{};
@@ -883,12 +867,15 @@ int seed_rows_pow2(const dpx_term* terms, int nterms, const float* rho, const fl
     for (int i = 0; i < nterms; ++i) ops[i] = terms[i].linop;
     if (seed_rows_seq_pow2(ops, nterms, rho, x0, spec, B * C, C, H, W, table, stream)) return launch_status("dpx_admm_seed_rows");
   }
-  switch (W) {
-    case 256: launch_seed<128, 16>(S_, rho, spec, nrows, H, C, tw_rows(table), stream); break;
-    case 512: launch_seed<256, 32>(S_, rho, spec, nrows, H, C, tw_rows(table), stream); break;
-    case 768: launch_seed<384, 64>(S_, rho, spec, nrows, H, C, tw_rows(table), stream); break;
-    default: launch_seed<512, 64>(S_, rho, spec, nrows, H, C, tw_rows(table), stream); break;
-  }
+  const bool launched = dispatch_rows_wave(W, [&](auto shape) {                // (dpx_admm_iter_supported: the wave map's widths)
+    constexpr int M = decltype(shape)::M, T = decltype(shape)::T, SPB = 256 / T;
+    dispatch_flag(x0 != nullptr, [&](auto fresh) {
+      DPX_LAUNCH("k_seed_rows", (k_seed_rows<M, T, decltype(fresh)::value>), dim3((nrows + SPB - 1) / SPB), dim3(256), 0, stream, S_, rho, spec,
+                 spec + (size_t)nrows * M, nrows, H, C, tw_rows(table));
+    });
+    return true;
+  });
+  if (!launched) launch_fail("k_seed_rows: no instantiation for %d-wide rows", W);
   return launch_status("dpx_admm_seed_rows");
 }
 
@@ -924,14 +911,6 @@ int spectral_apply_pow2(const float* x, float* y, int op, const SpecArgs& A, int
 }
 
 
-template <int M, int T>
-static void launch_pgd_rows(const float2* sin, float2* sout, float* x, const float* ktb, const float* rho, const float* lam, float alpha, int prox,
-                            int nrows, int H, int C, const float2* twW, hipStream_t s) {
-  constexpr int SPB = 256 / T;
-  DPX_LAUNCH("k_pgd_rows", (k_pgd_rows<M, T>), dim3((nrows + SPB - 1) / SPB), dim3(256), 0, s, sin, sout, x, ktb, rho, lam, alpha, prox, nrows, H,
-             C, twW);
-}
-
 bool pgd_rows_seq_pow2(const float2* sin, float2* sout, float* x, const float* ktb, const float* rho, const float* lam, float alpha, int prox, int P,
                        int C, int H, int W, const void* table, hipStream_t s);        // dpx_iter.hip: the streaming row pass
 
@@ -950,14 +929,13 @@ int pgd_run_pow2(float* x, const float* ktb, const void* gram_otf, int prox, flo
     const float* rho = rho_tab + (size_t)it * B;
     const float* lam = lam_tab ? lam_tab + (size_t)it * B : nullptr;
     if (pgd_rows_seq_pow2(spec2, sout, x, ktb, rho, lam, alpha, prox, P, C, H, W, table, stream)) continue;
-    switch (W) {
-      case 256: launch_pgd_rows<128, 16>(spec2, sout, x, ktb, rho, lam, alpha, prox, P * H, H, C, tw_rows(table), stream); break;
-      case 512: launch_pgd_rows<256, 32>(spec2, sout, x, ktb, rho, lam, alpha, prox, P * H, H, C, tw_rows(table), stream); break;
-      case 768: launch_pgd_rows<384, 16>(spec2, sout, x, ktb, rho, lam, alpha, prox, P * H, H, C, tw_rows(table), stream); break;
-      case 1536: launch_pgd_rows<768, 32>(spec2, sout, x, ktb, rho, lam, alpha, prox, P * H, H, C, tw_rows(table), stream); break;
-      case 1024: launch_pgd_rows<512, 64>(spec2, sout, x, ktb, rho, lam, alpha, prox, P * H, H, C, tw_rows(table), stream); break;
-      default: launch_pgd_rows<1024, 64>(spec2, sout, x, ktb, rho, lam, alpha, prox, P * H, H, C, tw_rows(table), stream); break;
-    }
+    const bool launched = dispatch_rows_plain(W, [&](auto shape) {
+      constexpr int M = decltype(shape)::M, T = decltype(shape)::T, SPB = 256 / T;
+      DPX_LAUNCH("k_pgd_rows", (k_pgd_rows<M, T>), dim3((P * H + SPB - 1) / SPB), dim3(256), 0, stream, spec2, sout, x, ktb, rho, lam, alpha, prox, P * H, H,
+                 C, tw_rows(table));
+      return true;
+    });
+    if (!launched) launch_fail("k_pgd_rows: no instantiation for %d-wide rows", W);
   }
   return launch_status("dpx_pgd_run");
 }

@@ -17,6 +17,30 @@ namespace dpx {
 __device__ __forceinline__ int lds_slot(int i) { return i + (i >> 4); }
 template <int N> struct LdsSeq { static constexpr int SLOTS = N + N / 16; };
 
+// Dynamic-LDS images of the row kernels: the kernel carves its pointers from these constants and its launcher asks for BYTES.
+// Lock-step kernels (k_iter_rows, k_bwd_rows; 256 threads = SPB rows in flight): SPB transform scratches, then two rings of
+// RING = SPB + RING_EXTRA rows of M pixel pairs.
+template <int M, int T, int RING_EXTRA> struct RingRowsLds {
+  static constexpr int SPB = 256 / T, S = LdsSeq<M>::SLOTS, RING = SPB + RING_EXTRA;
+  static constexpr size_t BYTES = (size_t)(SPB * S + 2 * RING * M) * sizeof(float2);
+};
+// Streaming and row-parallel kernels (k_iter_rows_seq / _par, k_pgd_rows_seq, k_seed_rows_seq, k_bwd_rows_par; NW waves of G = 64 / T
+// rows): M untangling and 64 pass-B twiddles, then per wave G transform scratches and NSTG staged row sets (STG = 64 V float2 =
+// G rows of M), followed by 32 slots for the rows' Nyquist bins where the staged rows are spectra (NYQ).
+template <int M, int T, int NW, int NSTG, bool NYQ> struct WaveRowsLds {
+  static constexpr int V = M / T, G = 64 / T, S = LdsSeq<M>::SLOTS, STG = 64 * V;
+  static constexpr int PERWAVE = G * S + NSTG * STG + (NYQ ? 32 : 0);
+  static constexpr int WAVES = M + 64;                   // slot of wave 0's area, behind the two twiddle tables
+  static constexpr size_t BYTES = (size_t)(WAVES + NW * PERWAVE) * sizeof(float2);
+};
+// One alias per kernel family, taking the kernel's own template arguments: kernel and launcher name the same layout.
+template <int M, int T> using IterRowsLds = RingRowsLds<M, T, 1>;                                      // k_iter_rows
+template <int M, int T> using BwdRowsLds = RingRowsLds<M, T, 2>;                                       // k_bwd_rows
+template <int M, int T, int NT, bool DUAL> using IterSeqLds = WaveRowsLds<M, T, 4, 1 + (DUAL ? NT : 0), true>;   // spectrum row + the streamed duals
+template <int M, int T, bool KTB> using PgdSeqLds = WaveRowsLds<M, T, 4, KTB ? 3 : 2, true>;          // spectrum row, x [, K^T b]
+template <int M, int T> using SeedSeqLds = WaveRowsLds<M, T, 4, 2, false>;                             // two rows of x0 in flight
+template <int M, int T, int NW> using RowsParLds = WaveRowsLds<M, T, NW, 1, true>;                     // k_iter_rows_par, k_bwd_rows_par
+
 // Experiment, OFF by default (-DDPX_FFT_BASEOFF=1 enables it): the slot of every LDS access of the three passes as  base(t) +
 // compile-time constant, so that the constant becomes the instruction's immediate offset (written as lds_slot(t-dependent index +
 // constant) the compiler re-derives `i + (i >> 4)` per access).  Valid for the splits the kernels use (checked exhaustively against

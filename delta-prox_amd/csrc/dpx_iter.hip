@@ -39,7 +39,8 @@ template <int M, int T, int NT>
 __global__ void __launch_bounds__(256, (M == 512 && NT >= 3) ? 1 : 2) k_iter_rows(const float2* __restrict__ spec_in, float2* __restrict__ spec_out, IterTerms TT,
                                                     const float* __restrict__ rho_next, float* __restrict__ x_out, int emit_v,
                                                     int C, int H, int R, int P, const float2* __restrict__ twW) {
-  constexpr int V = M / T, SPB = 256 / T, S = LdsSeq<M>::SLOTS, RING = SPB + 1;
+  using L = IterRowsLds<M, T>;
+  constexpr int V = M / T, SPB = L::SPB, S = L::S, RING = L::RING;
   HIP_DYNAMIC_SHARED(float2, smem_it)
   float2* fft_lds = smem_it;                          // SPB * S
   float2* xring = smem_it + SPB * S;                  // RING rows of M float2 (pixel pairs)
@@ -250,29 +251,6 @@ __global__ void __launch_bounds__(256, (M == 512 && NT >= 3) ? 1 : 2) k_iter_row
   }
 }
 
-static size_t iter_rows_lds(int M, int T) {
-  const int SPB = 256 / T, S = M + M / 16;
-  return (size_t)(SPB * S + 2 * (SPB + 1) * M) * sizeof(float2);
-}
-
-template <int M, int T, int NT>
-static void launch_iter_rows_nt(const float2* sin, float2* sout, const IterTerms& TT, const float* rho_next, float* x_out, int emit_v,
-                                int C, int H, int R, int P, const float2* twW, hipStream_t s) {
-  const size_t sh = iter_rows_lds(M, T);
-  DPX_LAUNCH_LDS("k_iter_rows", (k_iter_rows<M, T, NT>), dim3(P * (H / R)), dim3(256), sh, s, sin, sout, TT, rho_next, x_out, emit_v, C,
-                 H, R, P, twW);
-}
-template <int M, int T>
-static void launch_iter_rows(const float2* sin, float2* sout, const IterTerms& TT, const float* rho_next, float* x_out, int emit_v,
-                             int C, int H, int R, int P, const float2* twW, hipStream_t s) {
-  switch (TT.n) {
-    case 1: launch_iter_rows_nt<M, T, 1>(sin, sout, TT, rho_next, x_out, emit_v, C, H, R, P, twW, s); break;
-    case 2: launch_iter_rows_nt<M, T, 2>(sin, sout, TT, rho_next, x_out, emit_v, C, H, R, P, twW, s); break;
-    case 3: launch_iter_rows_nt<M, T, 3>(sin, sout, TT, rho_next, x_out, emit_v, C, H, R, P, twW, s); break;
-    default: launch_iter_rows_nt<M, T, 4>(sin, sout, TT, rho_next, x_out, emit_v, C, H, R, P, twW, s); break;
-  }
-}
-
 
 // ------------------------------------------------------------------------------------------------------------
 // k_iter_rows_seq: the same band update as k_iter_rows, organised so that HBM streams continuously.
@@ -308,14 +286,14 @@ __global__ void __launch_bounds__(256, (NT >= 4 || (NT == 3 && VXU && M == 256))
   constexpr int V = M / T, G = 64 / T, S = LdsSeq<M>::SLOTS, D = V / 2, RM = M / (V * V);
   constexpr int STG = 64 * V;                           // float2 per staged row set of one wave (G rows)
   constexpr int NU = DUAL ? NT : 0;                   // terms whose dual is streamed
-  constexpr int PERWAVE = G * S + STG + 32 + NU * STG;
+  using L = IterSeqLds<M, T, NT, DUAL>;
   HIP_DYNAMIC_SHARED(float2, smem_sq)
   float2* twl = smem_sq;                                // untangling twiddles exp(-i pi k / M), k < M
   float2* twb = smem_sq + M;                            // pass-B twiddles W_{V*RM}^j, j < 64
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int g = lane / T, t = lane % T, lbase = lane & ~(T - 1);
-  float2* wl = twb + 64 + wave * PERWAVE;
+  float2* wl = twl + L::WAVES + wave * L::PERWAVE;
   float2* myfft = wl + g * S;
   float2* stX = wl + G * S;
   float* stN = (float*)(stX + STG);
@@ -624,39 +602,6 @@ __global__ void __launch_bounds__(256, (NT >= 4 || (NT == 3 && VXU && M == 256))
   }
 }
 
-static size_t iter_rows_seq_lds(int M, int T, int NU) {
-  const int V = M / T, G = 64 / T, S = M + M / 16, STG = 64 * V;
-  return (size_t)(M + 64 + 4 * (G * S + STG + 32 + NU * STG)) * sizeof(float2);
-}
-template <int M, int T, int NT, bool DUAL, bool VXU = false>
-static void launch_iter_rows_seq_d(const float2* sin, float2* sout, const IterTerms& TT, const float* rho_next, float* x_out, int emit_v,
-                                   int C, int H, int R, int P, const float2* twW, hipStream_t s) {
-  const size_t sh = iter_rows_seq_lds(M, T, DUAL ? NT : 0);
-  const int groups = P * R, per_block = 4 * (64 / T);   // R = bands per plane here
-  DPX_LAUNCH_LDS(VXU ? "k_iter_rows_seq_vxu" : (DUAL ? "k_iter_rows_seq" : "k_iter_rows_seq_nodual"), (k_iter_rows_seq<M, T, NT, DUAL, VXU>),
-                 dim3(groups / per_block), dim3(256), sh, s, sin, sout, TT, rho_next, x_out, emit_v, C, H, R, P, twW);
-}
-template <int M, int T, int NT>
-static void launch_iter_rows_seq_nt(const float2* sin, float2* sout, const IterTerms& TT, const float* rho_next, float* x_out, int emit_v,
-                                    int C, int H, int R, int P, const float2* twW, hipStream_t s) {
-  const bool keep_dual = false;                                 // (half-quadratic splitting on the general kernel: bit-identical, 36 instead of 20 B per pixel)
-  // emit_v == 2 (x only: the last pass of a solve() that returns x alone) runs on the no-dual instantiation whatever the solver
-  if (emit_v == 2 && x_out && !rho_next) launch_iter_rows_seq_d<M, T, NT, false>(sin, sout, TT, rho_next, x_out, 2, C, H, R, P, twW, s);
-  else if (TT.vxu) launch_iter_rows_seq_d<M, T, NT, true, true>(sin, sout, TT, rho_next, x_out, emit_v ? 1 : 0, C, H, R, P, twW, s);
-  else if (TT.dual == 0.f && !keep_dual) launch_iter_rows_seq_d<M, T, NT, false>(sin, sout, TT, rho_next, x_out, emit_v ? 1 : 0, C, H, R, P, twW, s);
-  else launch_iter_rows_seq_d<M, T, NT, true>(sin, sout, TT, rho_next, x_out, emit_v ? 1 : 0, C, H, R, P, twW, s);
-}
-template <int M, int T>
-static void launch_iter_rows_seq(const float2* sin, float2* sout, const IterTerms& TT, const float* rho_next, float* x_out, int emit_v,
-                                 int C, int H, int R, int P, const float2* twW, hipStream_t s) {
-  switch (TT.n) {
-    case 1: launch_iter_rows_seq_nt<M, T, 1>(sin, sout, TT, rho_next, x_out, emit_v, C, H, R, P, twW, s); break;
-    case 2: launch_iter_rows_seq_nt<M, T, 2>(sin, sout, TT, rho_next, x_out, emit_v, C, H, R, P, twW, s); break;
-    case 3: launch_iter_rows_seq_nt<M, T, 3>(sin, sout, TT, rho_next, x_out, emit_v, C, H, R, P, twW, s); break;
-    default: launch_iter_rows_seq_nt<M, T, 4>(sin, sout, TT, rho_next, x_out, emit_v, C, H, R, P, twW, s); break;
-  }
-}
-
 // ------------------------------------------------------------------------------------------------------------
 // k_pgd_rows_seq: the row pass of a proximal-gradient iteration (k_pgd_rows, dpx_fft_pow2.hip; reference dprox/algo/pgd.py:26-54) on
 // the streaming structure of k_iter_rows_seq: one T-lane group walks down a band of rows; the next row's spectrum, iterate and K^T b
@@ -672,14 +617,14 @@ __global__ void __launch_bounds__(256, 2) k_pgd_rows_seq(const float2* __restric
   constexpr int V = M / T, G = 64 / T, S = LdsSeq<M>::SLOTS, D = V / 2, RM = M / (V * V);
   constexpr int STG = 64 * V;
   constexpr int NR = KTB ? 2 : 1;                       // image-row streams: x, K^T b
-  constexpr int PERWAVE = G * S + STG + 32 + NR * STG;
+  using L = PgdSeqLds<M, T, KTB>;
   HIP_DYNAMIC_SHARED(float2, smem_pq)
   float2* twl = smem_pq;
   float2* twb = smem_pq + M;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int g = lane / T, t = lane % T, lbase = lane & ~(T - 1);
-  float2* wl = twb + 64 + wave * PERWAVE;
+  float2* wl = twl + L::WAVES + wave * L::PERWAVE;
   float2* myfft = wl + g * S;
   float2* stX = wl + G * S;
   float* stN = (float*)(stX + STG);
@@ -818,42 +763,26 @@ __global__ void __launch_bounds__(256, 2) k_pgd_rows_seq(const float2* __restric
 // run-time overrides shared with the ADMM row kernels (dpx_admm_iter_config): rows_mode 2 keeps the plain kernels, bands_per_plane > 0
 // fixes the band count
 extern int g_rows_mode_pgd, g_rows_band_pgd, g_chain_share;
-template <int M, int T>
-static bool launch_pgd_rows_seq(const float2* sin, float2* sout, float* x, const float* ktb, const float* rho, const float* lam, float alpha, int prox,
-                                int C, int H, int P, const float2* twW, hipStream_t s) {
-  constexpr int V = M / T, G = 64 / T, S = M + M / 16, STG = 64 * V;
-  // bands per plane: a power of two, ~3 rounds of the resident T-lane groups (2 workgroups of 4 waves per CU) -- there is no halo
-  // to amortise here, and shorter bands even out the tail (8x3x1024^2: 64 / 128 / 256 bands 0.158 / 0.150 / 0.147 ms per iteration)
-  int nb = (256 * 2 * 4 * G) / (P * g_chain_share);
-  int p2 = 1;
-  while (p2 < nb) p2 <<= 1;
-  nb = 2 * p2;
-  const int band_env = 0;
-  if (band_env) nb = band_env;
-  if (g_rows_band_pgd > 0) nb = g_rows_band_pgd;
-  if (nb > H) nb = H;
-  const int per_block = 4 * G;
-  if (nb < 1 || H % nb || (P * nb) % per_block) return false;
-  const size_t sh1 = (size_t)(M + 64 + 4 * (G * S + STG + 32 + 1 * STG)) * sizeof(float2), sh2 = (size_t)(M + 64 + 4 * (G * S + STG + 32 + 2 * STG)) * sizeof(float2);
-  const dim3 grid(P * nb / per_block);
-  if (ktb)
-    DPX_LAUNCH_LDS("k_pgd_rows_seq", (k_pgd_rows_seq<M, T, true>), grid, dim3(256), sh2, s, sin, sout, x, ktb, rho, lam, alpha, prox, C, H, nb, P, twW);
-  else
-    DPX_LAUNCH_LDS("k_pgd_rows_seq", (k_pgd_rows_seq<M, T, false>), grid, dim3(256), sh1, s, sin, sout, x, ktb, rho, lam, alpha, prox, C, H, nb, P, twW);
-  return true;
-}
-// false: the plane / batch does not fit the streaming kernel (the caller keeps k_pgd_rows)
+// false: the plane / batch does not fit the streaming kernel (the caller keeps k_pgd_rows, which serves every plane)
 bool pgd_rows_seq_pow2(const float2* sin, float2* sout, float* x, const float* ktb, const float* rho, const float* lam, float alpha, int prox, int P,
                        int C, int H, int W, const void* table, hipStream_t s) {
-  const bool plain = false;                               // (the plain row kernel serves the planes the streaming one has no partition for)
-  if (plain || g_rows_mode_pgd == 2) return false;
-  switch (W) {
-    case 256: return launch_pgd_rows_seq<128, 16>(sin, sout, x, ktb, rho, lam, alpha, prox, C, H, P, tw_rows(table), s);
-    case 512: return launch_pgd_rows_seq<256, 32>(sin, sout, x, ktb, rho, lam, alpha, prox, C, H, P, tw_rows(table), s);
-    case 1024: return launch_pgd_rows_seq<512, 64>(sin, sout, x, ktb, rho, lam, alpha, prox, C, H, P, tw_rows(table), s);
-    case 768: return launch_pgd_rows_seq<384, 64>(sin, sout, x, ktb, rho, lam, alpha, prox, C, H, P, tw_rows(table), s);
-    default: return false;
-  }
+  if (g_rows_mode_pgd == 2) return false;
+  return dispatch_rows_wave(W, [&](auto shape) {
+    constexpr int M = decltype(shape)::M, T = decltype(shape)::T, per_block = 4 * (64 / T);
+    // bands per plane: a power of two, ~3 rounds of the resident T-lane groups (2 workgroups of 4 waves per CU) -- there is no halo
+    // to amortise here, and shorter bands even out the tail (8x3x1024^2: 64 / 128 / 256 bands 0.158 / 0.150 / 0.147 ms per iteration)
+    int nb = 2 * resident_bands_pow2(64 / T, P, g_chain_share);
+    if (g_rows_band_pgd > 0) nb = g_rows_band_pgd;
+    if (nb > H) nb = H;
+    if (nb < 1 || H % nb || (P * nb) % per_block) return false;
+    dispatch_flag(ktb != nullptr, [&](auto has_ktb) {
+      constexpr bool KTB = decltype(has_ktb)::value;
+      using L = PgdSeqLds<M, T, KTB>;
+      DPX_LAUNCH_LDS("k_pgd_rows_seq", (k_pgd_rows_seq<M, T, KTB>), dim3(P * nb / per_block), dim3(256), L::BYTES, s, sin, sout, x, ktb, rho, lam, alpha,
+                     prox, C, H, nb, P, tw_rows(table));
+    });
+    return true;
+  });
 }
 
 // ------------------------------------------------------------------------------------------------------------
@@ -878,14 +807,14 @@ __global__ void __launch_bounds__(256, 2) k_seed_rows_seq(SeedOps SO, const floa
                                                         float2* __restrict__ spec_out, int C, int H, int bands, int P, const float2* __restrict__ twW) {
   constexpr int V = M / T, G = 64 / T, S = LdsSeq<M>::SLOTS, D = V / 2, RM = M / (V * V);
   constexpr int STG = 64 * V;
-  constexpr int PERWAVE = G * S + 2 * STG;
+  using L = SeedSeqLds<M, T>;
   HIP_DYNAMIC_SHARED(float2, smem_sd)
   float2* twl = smem_sd;
   float2* twb = smem_sd + M;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int g = lane / T, t = lane % T, lbase = lane & ~(T - 1);
-  float2* wl = twb + 64 + wave * PERWAVE;
+  float2* wl = twl + L::WAVES + wave * L::PERWAVE;
   float2* myfft = wl + g * S;
   float2* stR = wl + G * S;
   for (int i = tid; i < M; i += 256) twl[i] = twW[i];
@@ -1006,37 +935,66 @@ __global__ void __launch_bounds__(256, 2) k_seed_rows_seq(SeedOps SO, const floa
   }
 }
 
-template <int M, int T>
-static bool launch_seed_rows_seq(const SeedOps& SO, const float* rho, const float* x0, float2* spec, int C, int H, int P, const float2* twW, hipStream_t s) {
-  constexpr int V = M / T, G = 64 / T, S = M + M / 16, STG = 64 * V;
-  // bands per plane: the row kernel's rule (every T-lane group of the launch resident, rounded up to a power of two)
-  int nb = (256 * 2 * 4 * G) / (P * g_chain_share), p2 = 1;
-  while (p2 < nb) p2 <<= 1;
-  nb = p2;
-  const int band_env = 0;
-  if (band_env) nb = band_env;
-  if (nb > H / 4) nb = H / 4;
-  const int per_block = 4 * G;
-  if (nb < 1 || H % nb || (P * nb) % per_block) return false;
-  const size_t sh = (size_t)(M + 64 + 4 * (G * S + 2 * STG)) * sizeof(float2);
-  DPX_LAUNCH_LDS("k_seed_rows_seq", (k_seed_rows_seq<M, T>), dim3(P * nb / per_block), dim3(256), sh, s, SO, rho, x0, spec, C, H, nb, P, twW);
-  return true;
-}
 // false: the plane / batch does not fit the streaming kernel (the caller keeps k_seed_rows<FRESH>)
 bool seed_rows_seq_pow2(const int* linops, int n, const float* rho, const float* x0, float2* spec, int P, int C, int H, int W, const void* table,
                         hipStream_t s) {
-  const bool plain = false;
-  if (plain || g_rows_mode_pgd == 2) return false;                 // (dpx_admm_iter_config: 2 = the plain kernels)
+  if (g_rows_mode_pgd == 2) return false;                 // (dpx_admm_iter_config: 2 = the plain kernels)
   SeedOps SO{};
   SO.n = n;
   for (int i = 0; i < n; ++i) SO.linop[i] = linops[i];
-  switch (W) {
-    case 256: return launch_seed_rows_seq<128, 16>(SO, rho, x0, spec, C, H, P, tw_rows(table), s);
-    case 512: return launch_seed_rows_seq<256, 32>(SO, rho, x0, spec, C, H, P, tw_rows(table), s);
-    case 1024: return launch_seed_rows_seq<512, 64>(SO, rho, x0, spec, C, H, P, tw_rows(table), s);
-    case 768: return launch_seed_rows_seq<384, 64>(SO, rho, x0, spec, C, H, P, tw_rows(table), s);
-    default: return false;
-  }
+  return dispatch_rows_wave(W, [&](auto shape) {
+    constexpr int M = decltype(shape)::M, T = decltype(shape)::T, per_block = 4 * (64 / T);
+    // bands per plane: the row kernel's rule, bands of at least 4 rows (two rows are in flight per group)
+    int nb = resident_bands_pow2(64 / T, P, g_chain_share);
+    if (nb > H / 4) nb = H / 4;
+    if (nb < 1 || H % nb || (P * nb) % per_block) return false;
+    DPX_LAUNCH_LDS("k_seed_rows_seq", (k_seed_rows_seq<M, T>), dim3(P * nb / per_block), dim3(256), (SeedSeqLds<M, T>::BYTES), s, SO, rho,
+                   x0, spec, C, H, nb, P, tw_rows(table));
+    return true;
+  });
+}
+
+// ------------------------------------------------------------------------------------------------------------
+// The launchers of dpx_admm_iter_rows' two kernels of this file (the row-parallel one: launch_iter_rows_par, dpx_iter_par.hip)
+
+// workgroups of 4 waves of G = 64 / T band walkers each: the groups of a launch must fill whole workgroups (0: no streaming kernel for W)
+static int seq_groups_per_block(int W) {
+  const int T = rows_wave_lanes(W);
+  return T ? 4 * (64 / T) : 0;
+}
+// `bands` bands per plane; P * bands is a multiple of seq_groups_per_block(W) (the caller's check)
+static bool launch_iter_rows_seq(int W, const float2* sin, float2* sout, const IterTerms& TT, const float* rho_next, float* x_out, int emit_v, int C,
+                                 int H, int bands, int P, const float2* twW, hipStream_t s) {
+  const IterVariant var = iter_variant(TT, emit_v, x_out, rho_next);
+  return dispatch_rows_wave(W, [&](auto shape) {
+    dispatch_nterms(TT.n, [&](auto nt) {
+      dispatch_iter_variant(var, [&](auto dual, auto vxu) {
+        constexpr int M = decltype(shape)::M, T = decltype(shape)::T, NT = decltype(nt)::value;
+        constexpr bool DUAL = decltype(dual)::value, VXU = decltype(vxu)::value;
+        using L = IterSeqLds<M, T, NT, DUAL>;
+        DPX_LAUNCH_LDS(VXU ? "k_iter_rows_seq_vxu" : (DUAL ? "k_iter_rows_seq" : "k_iter_rows_seq_nodual"), (k_iter_rows_seq<M, T, NT, DUAL, VXU>),
+                       dim3(P * bands / (4 * L::G)), dim3(256), L::BYTES, s, sin, sout, TT, rho_next, x_out, var.emit_v, C, H, bands, P, twW);
+      });
+    });
+    return true;
+  });
+}
+
+// (the lock-step kernel exists for the power-of-two widths, M = 8 T: 256, 512 and 1024)
+static bool launch_iter_rows(int W, const float2* sin, float2* sout, const IterTerms& TT, const float* rho_next, float* x_out, int emit_v, int C, int H,
+                             int R, int P, const float2* twW, hipStream_t s) {
+  return dispatch_rows_plain(W, [&](auto shape) {
+    constexpr int M = decltype(shape)::M, T = decltype(shape)::T;
+    if constexpr (M != 8 * T) return false;
+    else {
+      dispatch_nterms(TT.n, [&](auto nt) {
+        constexpr int NT = decltype(nt)::value;
+        DPX_LAUNCH_LDS("k_iter_rows", (k_iter_rows<M, T, NT>), dim3(P * (H / R)), dim3(256), (IterRowsLds<M, T>::BYTES), s, sin, sout, TT, rho_next,
+                       x_out, emit_v, C, H, R, P, twW);
+      });
+      return true;
+    }
+  });
 }
 
 size_t pow2_spec_elems(int P, int H, int W);
@@ -1067,6 +1025,7 @@ static int terms_ok(const dpx_term* terms, int nterms) {
 
 // run-time overrides of the row-kernel choice (tests / tuning): rows_mode 0 = automatic, 1 = streaming kernel, 2 = lock-step
 // ring-buffer kernel; bands_per_plane 0 = automatic.  The environment variables DPX_ITER_ROWS / DPX_ITER_BAND set the defaults.
+enum RowsMode { ROWS_AUTO = 0, ROWS_SEQ = 1, ROWS_LOCKSTEP = 2, ROWS_PAR = 3 };      // dpx_admm_iter_config's rows_mode / the iter_rows knob
 static int g_rows_mode = -1, g_rows_band = -1;
 namespace dpx { int g_rows_mode_pgd = 0, g_rows_band_pgd = 0, g_chain_share = 1; int iter_seq_bands(int P, int H, int W, int forced); }
 // Sub-batches of one solve running as independent chains on separate streams (dprox/algo/fused.py) share the GPU: the row kernels size
@@ -1078,13 +1037,9 @@ namespace dpx { int g_rows_mode_pgd = 0, g_rows_band_pgd = 0, g_chain_share = 1;
 // `iter_band_min_rows` (4) rows long, and such that the groups fill whole workgroups.  A partition always exists: if no count below
 // the rule's fills whole workgroups (P odd and large), the smallest count that does is taken (per_block / gcd(P, per_block) <= 16).
 int dpx::iter_seq_bands(int P, int H, int W, int forced) {
-  const int T = W == 768 ? 64 : W / 16, G = 64 / T, per_block = 4 * G;
-  int nb = (256 * 2 * 4 * G) / (P * dpx::g_chain_share);
-  {
-    int p2 = 1;
-    while (p2 < nb) p2 <<= 1;
-    nb = p2;
-  }
+  const int per_block = seq_groups_per_block(W);
+  if (!per_block) return 0;                              // (no streaming kernel for W: no partition)
+  int nb = resident_bands_pow2(per_block / 4, P, dpx::g_chain_share);
   if (forced) nb = forced;
   const int min_rows_knob = tune(TUNE_ITER_BAND_MIN_ROWS);
   const int min_rows = min_rows_knob > 0 ? min_rows_knob : 4;
@@ -1199,28 +1154,21 @@ int dpx::iter_rows_impl(const void* spec_in, void* spec_out, const dpx_term* ter
   const float2* sin = (const float2*)spec_in;
   float2* sout = (float2*)spec_out;
   // Streaming kernel (one T-lane group per band): bands as long as possible while still >= ~2 waves per SIMD-pair
-  // of the chip; DPX_ITER_ROWS=lockstep keeps the ring-buffer kernel (A/B timing), DPX_ITER_BAND overrides the number of bands per plane.
-  const int mode_knob = tune(TUNE_ITER_ROWS), band_env0 = tune(TUNE_ITER_BAND);
-  const char* mode_env = mode_knob == 1 ? "seq" : (mode_knob == 2 ? "lockstep" : (mode_knob == 3 ? "par" : nullptr));
-  const char* mode = g_rows_mode > 0 ? (g_rows_mode == 1 ? "seq" : (g_rows_mode == 2 ? "lockstep" : "par")) : (g_rows_mode == 0 ? nullptr : mode_env);
+  // of the chip; mode ROWS_LOCKSTEP keeps the ring-buffer kernel (A/B timing), the band knob overrides the number of bands per plane.
+  // precedence: dpx_admm_iter_config (0 = automatic, too) over the iter_rows knob
+  const int mode_knob = tune(TUNE_ITER_ROWS);
+  const RowsMode mode = (RowsMode)(g_rows_mode >= 0 ? g_rows_mode : (mode_knob >= 1 && mode_knob <= 3 ? mode_knob : 0));
   // launches of a few planes: the rows of a band side by side (dpx_iter_par.hip; bit-identical to the streaming kernel)
-  if (!mode || !strcmp(mode, "par")) {
-    if (launch_iter_rows_par(sin, sout, TT, rho_next, x_out, emit_v, C, H, W, P, tw, s, mode != nullptr)) return launch_status("dpx_admm_iter_rows");
+  if (mode == ROWS_AUTO || mode == ROWS_PAR) {
+    if (launch_iter_rows_par(sin, sout, TT, rho_next, x_out, emit_v, C, H, W, P, tw, s, mode == ROWS_PAR)) return launch_status("dpx_admm_iter_rows");
   }
-  const int band_env = g_rows_band >= 0 ? g_rows_band : band_env0;
   // (small launches -- a few 256-wide planes -- are latency-bound: the ring-buffer kernel's row-parallel bands finish ~10 %
   //  sooner there than the streaming kernel's sequential ones; measured crossover between 256- and 512-wide planes)
-  const bool tiny = W <= 256 && (long)P * H <= 4096 && !(mode && !strcmp(mode, "seq"));
-  if ((!(mode && !strcmp(mode, "lockstep")) && W <= 1024 && !tiny) || W == 768) {      // (768-wide rows exist on the streaming kernel only)
-    const int T = W == 768 ? 64 : W / 16, G = 64 / T, per_block = 4 * G;
-    const int nb = dpx::iter_seq_bands(P, H, W, band_env);
-    if (nb >= 1 && (P * nb) % per_block == 0) {
-      switch (W) {
-        case 256: launch_iter_rows_seq<128, 16>(sin, sout, TT, rho_next, x_out, emit_v, C, H, nb, P, tw, s); break;
-        case 512: launch_iter_rows_seq<256, 32>(sin, sout, TT, rho_next, x_out, emit_v, C, H, nb, P, tw, s); break;
-        case 768: launch_iter_rows_seq<384, 64>(sin, sout, TT, rho_next, x_out, emit_v, C, H, nb, P, tw, s); break;
-        default: launch_iter_rows_seq<512, 64>(sin, sout, TT, rho_next, x_out, emit_v, C, H, nb, P, tw, s); break;
-      }
+  const bool tiny = W <= 256 && (long)P * H <= 4096 && mode != ROWS_SEQ;
+  if ((mode != ROWS_LOCKSTEP && W <= 1024 && !tiny) || W == 768) {      // (768-wide rows exist on the streaming kernel only)
+    const int nb = dpx::iter_seq_bands(P, H, W, g_rows_band >= 0 ? g_rows_band : tune(TUNE_ITER_BAND));
+    if (nb >= 1 && (P * nb) % seq_groups_per_block(W) == 0) {      // (nb >= 1: W has a streaming kernel, seq_groups_per_block(W) > 0)
+      if (!launch_iter_rows_seq(W, sin, sout, TT, rho_next, x_out, emit_v, C, H, nb, P, tw, s)) launch_fail("k_iter_rows_seq: no instantiation for %d-wide planes", W);
       return launch_status("dpx_admm_iter_rows");
     }
   }
@@ -1229,12 +1177,28 @@ int dpx::iter_rows_impl(const void* spec_in, void* spec_out, const dpx_term* ter
   // (256-wide planes: 16 rows are in flight per workgroup, so a band of 8 rows + its 2 halo rows is ONE step of the kernel instead
   //  of two -- these launches are latency-bound: config 1 0.78 -> 0.62 ms per 20-iteration solve)
   const int R = r_env ? r_env : (W <= 256 ? 8 : 16);
-  switch (W) {
-    case 256: launch_iter_rows<128, 16>(sin, sout, TT, rho_next, x_out, emit_v ? 1 : 0, C, H, R, P, tw, s); break;
-    case 512: launch_iter_rows<256, 32>(sin, sout, TT, rho_next, x_out, emit_v ? 1 : 0, C, H, R, P, tw, s); break;
-    default: launch_iter_rows<512, 64>(sin, sout, TT, rho_next, x_out, emit_v ? 1 : 0, C, H, R, P, tw, s); break;
-  }
+  if (!launch_iter_rows(W, sin, sout, TT, rho_next, x_out, emit_v ? 1 : 0, C, H, R, P, tw, s)) launch_fail("k_iter_rows: no instantiation for %d-wide planes", W);
   return launch_status("dpx_admm_iter_rows");
+}
+
+// Iteration `it` of `total_iters`, the k-th of n_iters of this call, for one chain: the column pass spec_a -> spec_b (out of place; in place
+// was a round-2 experiment without gain), then the row pass back into spec_a with the chain's duals read from / written to the side the
+// parity names.  cur: the chain's working copy of its terms.
+static int admm_iteration(const dpx_chain& ch, dpx_term* cur, int nterms, const void* dd, float eps, int it, int k, int n_iters, int total_iters, int parity,
+                          int emit_last, int C, int H, int W, const void* table) {
+  const bool last_of_solve = (it == total_iters - 1);
+  const bool emit = emit_last && (k == n_iters - 1);
+  int rc = dpx_admm_iter_cols(ch.spec_a, ch.spec_b, ch.spec_add, dd, ch.rho_tab + (size_t)it * ch.B, eps, ch.B, C, H, W, table, ch.stream);
+  if (rc) return rc;
+  for (int i = 0; i < nterms; ++i) {
+    cur[i].lam = ch.lam_tabs[i] ? ch.lam_tabs[i] + (size_t)it * ch.B : nullptr;
+    if (k > 0) cur[i].reserved &= ~DPX_TERM_U_ZERO;      // (only the duals the call starts from can be the fresh zeros)
+    cur[i].u = parity ? ch.terms[i].u_out : ch.terms[i].u;
+    cur[i].u_out = parity ? ch.terms[i].u : ch.terms[i].u_out;
+  }
+  return dpx_admm_iter_rows(ch.spec_b, last_of_solve ? nullptr : ch.spec_a, cur, nterms,
+                            last_of_solve ? nullptr : ch.rho_tab + (size_t)(it + 1) * ch.B, emit ? ch.x_out : nullptr,
+                            emit ? (emit_last == 2 && last_of_solve ? 2 : 1) : 0, ch.B, C, H, W, table, ch.stream);
 }
 
 // Runs `n_iters` consecutive iterations (it0 .. it0 + n_iters - 1 of `total_iters`) without returning to the host
@@ -1252,30 +1216,13 @@ extern "C" int dpx_admm_run(void* spec_a, void* spec_b, const void* spec_add, co
   dpx_term cur[DPX_MAX_TERMS];
   DPX_REQUIRE(nterms >= 1 && nterms <= DPX_MAX_TERMS, "dpx_admm_run: nterms");
   for (int i = 0; i < nterms; ++i) cur[i] = terms[i];
+  dpx_chain ch{};
+  ch.spec_a = spec_a, ch.spec_b = spec_b, ch.spec_add = spec_add;
+  ch.terms = terms, ch.rho_tab = rho_tab, ch.lam_tabs = lam_tabs;
+  ch.x_out = x_out, ch.B = B, ch.stream = stream;
   int parity = 0;
-  const bool cols_inplace = false;                           // (column pass in place: a round-2 experiment, no gain)
   for (int k = 0; k < n_iters; ++k) {
-    const int it = it0 + k;
-    const bool last_of_solve = (it == total_iters - 1);
-    const bool emit = emit_last && (k == n_iters - 1);
-    if (cols_inplace) {
-      // column pass in place (every workgroup reads its whole tile before it writes it); the row pass then needs the other buffer
-      void* t = spec_a; spec_a = spec_b; spec_b = t;
-      int rc0 = dpx_admm_iter_cols(spec_b, spec_b, spec_add, dd, rho_tab + (size_t)it * B, eps, B, C, H, W, table, stream);
-      if (rc0) return rc0;
-    }
-    int rc = cols_inplace ? 0 : dpx_admm_iter_cols(spec_a, spec_b, spec_add, dd, rho_tab + (size_t)it * B, eps, B, C, H, W, table, stream);
-    if (rc) return rc;
-    for (int i = 0; i < nterms; ++i) {
-      cur[i].lam = lam_tabs[i] ? lam_tabs[i] + (size_t)it * B : nullptr;
-      if (k > 0) cur[i].reserved &= ~DPX_TERM_U_ZERO;      // (only the duals the call starts from can be the fresh zeros)
-      cur[i].u = parity ? terms[i].u_out : terms[i].u;
-      cur[i].u_out = parity ? terms[i].u : terms[i].u_out;
-    }
-    rc = dpx_admm_iter_rows(spec_b, last_of_solve ? nullptr : spec_a, cur, nterms,
-                            last_of_solve ? nullptr : rho_tab + (size_t)(it + 1) * B, emit ? x_out : nullptr,
-                            emit ? (emit_last == 2 && last_of_solve ? 2 : 1) : 0, B, C,
-                            H, W, table, stream);
+    const int rc = admm_iteration(ch, cur, nterms, dd, eps, it0 + k, k, n_iters, total_iters, parity, emit_last, C, H, W, table);
     if (rc) return rc;
     parity ^= 1;
   }
@@ -1345,10 +1292,9 @@ extern "C" int dpx_stream_join(dpx_stream_t into, const dpx_stream_t* from, int 
 
 // The same loop for `nchains` sub-batches of one solve, each on its own stream (the images of a batch never exchange data: one
 // chain's column pass can run beside another chain's row pass).  Launches are issued chain by chain within an iteration, so that every
-// chain has work queued from the first microseconds on; the chains then run freely.  (DPX_CHAIN_LOCKSTEP=1, measured and kept as a
-// switch: the column passes ordered by events -- chain c's of iteration k behind chain c-1's, chain 0's of iteration k+1 behind the last
-// chain's of iteration k.  It removes the drift between the chains -- left to the queues' arbitration one chain of two finishes ~12 %
-// earlier -- but also forbids column pass beside column pass and row pass beside row pass: 0.174 -> 0.202 ms per iteration at 8x3x1024^2.)
+// chain has work queued from the first microseconds on; the chains then run freely.  (Measured and removed: the column passes ordered
+// by events, chain after chain -- no drift between the chains, where one of two otherwise finishes ~12 % earlier, but no column pass
+// beside column pass either: 0.174 -> 0.202 ms per iteration at 8x3x1024^2.)
 // Returns the dual-buffer parity (the same for every chain), < 0 on error.
 extern "C" int dpx_admm_run_chains(const dpx_chain* chains, int nchains, const void* dd, int nterms, float eps, int it0, int n_iters,
                                    int total_iters, int emit_last, int C, int H, int W, const void* table) {
@@ -1360,11 +1306,6 @@ extern "C" int dpx_admm_run_chains(const dpx_chain* chains, int nchains, const v
     DPX_REQUIRE(ch.spec_a && ch.spec_b && ch.terms && ch.rho_tab && ch.lam_tabs && ch.B >= 1, "dpx_admm_run_chains: chain %d: null pointer", c);
     DPX_REQUIRE(!emit_last || ch.x_out, "dpx_admm_run_chains: emit_last needs x_out (chain %d)", c);
   }
-  ChainEvents* Ep = chain_events("dpx_admm_run_chains");
-  if (!Ep) return DPX_ERR_LAUNCH;
-  ChainEvents& E = *Ep;
-  const bool lockstep = false;                          // (chains in lock step: measured slower, round 3; the ordered form below stays for reference runs)
-  const bool ordered = lockstep && nchains > 1;
   dpx_term cur[DPX_MAX_CHAINS][DPX_MAX_TERMS];
   for (int c = 0; c < nchains; ++c)
     for (int i = 0; i < nterms; ++i) cur[c][i] = chains[c].terms[i];
@@ -1381,33 +1322,8 @@ extern "C" int dpx_admm_run_chains(const dpx_chain* chains, int nchains, const v
   }
   int parity = 0;
   for (int k = 0; k < n_iters; ++k) {
-    const int it = it0 + k;
-    const bool last_of_solve = (it == total_iters - 1);
-    const bool emit = emit_last && (k == n_iters - 1);
     for (int c = 0; c < nchains; ++c) {
-      const dpx_chain& ch = chains[c];
-      hipStream_t s = (hipStream_t)ch.stream;
-      if (ordered && (k > 0 || c > 0)) {
-        if (hipStreamWaitEvent(s, E.ev[(c + nchains - 1) % nchains], 0) != hipSuccess) {
-          set_error("dpx_admm_run_chains: hipStreamWaitEvent failed");
-          return DPX_ERR_LAUNCH;
-        }
-      }
-      int rc = dpx_admm_iter_cols(ch.spec_a, ch.spec_b, ch.spec_add, dd, ch.rho_tab + (size_t)it * ch.B, eps, ch.B, C, H, W, table, ch.stream);
-      if (rc) return rc;
-      if (ordered && hipEventRecord(E.ev[c], s) != hipSuccess) {
-        set_error("dpx_admm_run_chains: hipEventRecord failed");
-        return DPX_ERR_LAUNCH;
-      }
-      for (int i = 0; i < nterms; ++i) {
-        cur[c][i].lam = ch.lam_tabs[i] ? ch.lam_tabs[i] + (size_t)it * ch.B : nullptr;
-        if (k > 0) cur[c][i].reserved &= ~DPX_TERM_U_ZERO;
-        cur[c][i].u = parity ? ch.terms[i].u_out : ch.terms[i].u;
-        cur[c][i].u_out = parity ? ch.terms[i].u : ch.terms[i].u_out;
-      }
-      rc = dpx_admm_iter_rows(ch.spec_b, last_of_solve ? nullptr : ch.spec_a, cur[c], nterms,
-                              last_of_solve ? nullptr : ch.rho_tab + (size_t)(it + 1) * ch.B, emit ? ch.x_out : nullptr,
-                              emit ? (emit_last == 2 && last_of_solve ? 2 : 1) : 0, ch.B, C, H, W, table, ch.stream);
+      const int rc = admm_iteration(chains[c], cur[c], nterms, dd, eps, it0 + k, k, n_iters, total_iters, parity, emit_last, C, H, W, table);
       if (rc) return rc;
     }
     parity ^= 1;

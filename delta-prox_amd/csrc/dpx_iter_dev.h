@@ -1,6 +1,7 @@
 // Device-side declarations shared by the row kernels of the two-kernel ADMM iteration (dpx_iter.hip: the streaming and the lock-step
 // kernel; dpx_iter_par.hip: the row-parallel kernel of launches with few planes).  Not part of the C ABI.
 #pragma once
+#include "dpx_dispatch.h"
 #include "dpx_fft_reg.h"
 
 namespace dpx {
@@ -56,6 +57,26 @@ template <int V> __device__ __forceinline__ void soft_threshold_pairs(const floa
 #pragma unroll
     for (int m = 0; m < V; ++m) v[m] = make_float2(prox1(DPX_PROX_NORM1, d[m].x, lam), prox1(DPX_PROX_NORM1, d[m].y, lam));
   }
+}
+
+// The instantiation of the streaming (k_iter_rows_seq) and of the row-parallel (k_iter_rows_par) kernel that serves a pass, and the
+// emit_v it is handed: ONE rule for both, which is what keeps the row-parallel kernel bit-identical to the streaming one.
+struct IterVariant {
+  bool dual, vxu;
+  int emit_v;
+};
+static inline IterVariant iter_variant(const IterTerms& TT, int emit_v, const float* x_out, const float* rho_next) {
+  // emit_v == 2 (x only: the last pass of a solve() that returns x alone) runs on the no-dual instantiation whatever the solver
+  if (emit_v == 2 && x_out && !rho_next) return {false, false, 2};
+  if (TT.vxu) return {true, true, emit_v ? 1 : 0};
+  // (half-quadratic splitting on the general kernel would be bit-identical at 36 instead of 20 B per pixel)
+  return {TT.dual != 0.f, false, emit_v ? 1 : 0};
+}
+// f(DUAL tag, VXU tag) for the three forms that exist (VXU is a DUAL form)
+template <class F> static inline void dispatch_iter_variant(const IterVariant& v, F&& f) {
+  if (!v.dual) f(std::false_type{}, std::false_type{});
+  else if (v.vxu) f(std::true_type{}, std::true_type{});
+  else f(std::true_type{}, std::false_type{});
 }
 
 // Cache policy of the row kernels' four streams (dpx_common.h): spectrum in / u in (loads, 1 = nt), u out / spectrum out

@@ -50,17 +50,18 @@ __global__ void __launch_bounds__(64 * NW, 1) k_iter_rows_par(const float2* __re
   //  preloaded into scalar registers at wave launch, -mllvm -amdgpu-kernarg-preload-count=16 -- the by-value term table last)
   constexpr int V = M / T, G = 64 / T, S = LdsSeq<M>::SLOTS, D = V / 2, RM = M / (V * V);
   constexpr int STG = 64 * V;                           // float2 per staged row set of one wave (G rows of M)
-  constexpr int PERWAVE = G * S + STG + 32;
+  using L = RowsParLds<M, T, NW>;
+  constexpr int PERWAVE = L::PERWAVE;
   constexpr int RW = NW * G;                            // rows in flight per workgroup
   static_assert(V == 8 && STG + 32 == G * S, "the staging area doubles as the forward transform's scratch");
   HIP_DYNAMIC_SHARED(float2, smem_pr)
   float2* twl = smem_pr;                                // untangling twiddles exp(-i pi k / M), k < M
   float2* twb = smem_pr + M;                            // pass-B twiddles W_{V*RM}^j, j < 64
-  float2* waves = twb + 64;
+  float2* waves = twl + L::WAVES;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int g = lane / T, t = lane % T, lbase = lane & ~(T - 1);
-  float2* wl = waves + wave * PERWAVE;
+  float2* wl = waves + wave * L::PERWAVE;
   float2* myfft = wl + g * S;                           // inverse transform's scratch; then this row's w (grad_H term) for the row below
   float2* stX = wl + G * S;                             // DMA staging of the spectrum rows; then x of this wave's rows; then forward scratch
   float* stN = (float*)(stX + STG);
@@ -352,40 +353,6 @@ __global__ void __launch_bounds__(64 * NW, 1) k_iter_rows_par(const float2* __re
   }
 }
 
-template <int M, int T, int NT, bool DUAL, bool VXU>
-static void launch_par_d(const float2* sin, float2* sout, const IterTerms& TT, const float* rho_next, float* x_out, int emit_v, int C, int H, int P,
-                         const float2* twW, hipStream_t s) {
-  // 16 waves (128 registers each) for the one- and two-term forms; three or four terms and the v, x, u order keep more rows of duals / split
-  // variables in registers: 8 waves of 256 registers (no scratch in any instantiation: tools/spill_check.py)
-  constexpr int NW = (NT >= 3 || VXU) ? 8 : 16, G = 64 / T, S = M + M / 16, V = M / T, RW = NW * G;
-  const size_t sh = (size_t)(M + 64 + NW * (G * S + 64 * V + 32)) * sizeof(float2);
-  const bool xonly = !DUAL && emit_v == 2;
-  const int rows = xonly ? RW : RW - 2;                 // own rows per workgroup
-  const int bands = (H + rows - 1) / rows;
-  DPX_LAUNCH_LDS(VXU ? "k_iter_rows_par_vxu" : (DUAL ? "k_iter_rows_par" : "k_iter_rows_par_nodual"), (k_iter_rows_par<M, T, NT, DUAL, VXU, NW>),
-                 dim3(P * bands), dim3(64 * NW), sh, s, sin, sout, twW, rho_next, x_out, emit_v, C, H, bands, P, TT);
-}
-template <int M, int T, int NT>
-static void launch_par_nt(const float2* sin, float2* sout, const IterTerms& TT, const float* rho_next, float* x_out, int emit_v, int C, int H, int P,
-                          const float2* twW, hipStream_t s) {
-  const bool keep_dual = false;
-  // (the same choice of instantiation as launch_iter_rows_seq_nt, dpx_iter.hip)
-  if (emit_v == 2 && x_out && !rho_next) launch_par_d<M, T, NT, false, false>(sin, sout, TT, rho_next, x_out, 2, C, H, P, twW, s);
-  else if (TT.vxu) launch_par_d<M, T, NT, true, true>(sin, sout, TT, rho_next, x_out, emit_v ? 1 : 0, C, H, P, twW, s);
-  else if (TT.dual == 0.f && !keep_dual) launch_par_d<M, T, NT, false, false>(sin, sout, TT, rho_next, x_out, emit_v ? 1 : 0, C, H, P, twW, s);
-  else launch_par_d<M, T, NT, true, false>(sin, sout, TT, rho_next, x_out, emit_v ? 1 : 0, C, H, P, twW, s);
-}
-template <int M, int T>
-static void launch_par(const float2* sin, float2* sout, const IterTerms& TT, const float* rho_next, float* x_out, int emit_v, int C, int H, int P,
-                       const float2* twW, hipStream_t s) {
-  switch (TT.n) {
-    case 1: launch_par_nt<M, T, 1>(sin, sout, TT, rho_next, x_out, emit_v, C, H, P, twW, s); break;
-    case 2: launch_par_nt<M, T, 2>(sin, sout, TT, rho_next, x_out, emit_v, C, H, P, twW, s); break;
-    case 3: launch_par_nt<M, T, 3>(sin, sout, TT, rho_next, x_out, emit_v, C, H, P, twW, s); break;
-    default: launch_par_nt<M, T, 4>(sin, sout, TT, rho_next, x_out, emit_v, C, H, P, twW, s); break;
-  }
-}
-
 // Row-parallel kernel for launches that cannot fill the chip with band walkers: P * H rows up to `iter_par_max_rows` (knob; the
 // library's rule: 8192 rows of 1024 / 512 / 256 pixels -- 1 .. 2 rounds of one 16-wave workgroup per CU), or forced (iter_rows = 3).
 bool launch_iter_rows_par(const float2* sin, float2* sout, const IterTerms& TT, const float* rho_next, float* x_out, int emit_v, int C, int H, int W,
@@ -398,12 +365,28 @@ bool launch_iter_rows_par(const float2* sin, float2* sout, const IterTerms& TT, 
     // (a few 256-wide planes -- config 1 -- stay on the lock-step kernel's 8-row bands: 0.580 ms per 20-iteration solve against 0.606 here)
     if (W <= 256 && (long)P * H <= 4096 && knob == 0) return false;
   }
-  switch (W) {
-    case 256: launch_par<128, 16>(sin, sout, TT, rho_next, x_out, emit_v, C, H, P, twW, s); break;
-    case 512: launch_par<256, 32>(sin, sout, TT, rho_next, x_out, emit_v, C, H, P, twW, s); break;
-    default: launch_par<512, 64>(sin, sout, TT, rho_next, x_out, emit_v, C, H, P, twW, s); break;
-  }
-  return true;
+  const IterVariant var = iter_variant(TT, emit_v, x_out, rho_next);
+  return dispatch_rows_wave(W, [&](auto shape) {
+    constexpr int M = decltype(shape)::M, T = decltype(shape)::T;
+    if constexpr (M != 8 * T) return false;                // (k_iter_rows_par: eight values per lane -- the three widths above)
+    else {
+      dispatch_nterms(TT.n, [&](auto nt) {
+        dispatch_iter_variant(var, [&](auto dual, auto vxu) {
+          constexpr int NT = decltype(nt)::value;
+          constexpr bool DUAL = decltype(dual)::value, VXU = decltype(vxu)::value;
+          // 16 waves (128 registers each) for the one- and two-term forms; three or four terms and the v, x, u order keep more rows of duals / split
+          // variables in registers: 8 waves of 256 registers (no scratch in any instantiation: tools/spill_check.py)
+          constexpr int NW = (NT >= 3 || VXU) ? 8 : 16, RW = NW * (64 / T);
+          const int rows = var.emit_v == 2 ? RW : RW - 2;    // own rows per workgroup (x only: no halo rows)
+          const int bands = (H + rows - 1) / rows;
+          DPX_LAUNCH_LDS(VXU ? "k_iter_rows_par_vxu" : (DUAL ? "k_iter_rows_par" : "k_iter_rows_par_nodual"), (k_iter_rows_par<M, T, NT, DUAL, VXU, NW>),
+                         dim3(P * bands), dim3(64 * NW), (RowsParLds<M, T, NW>::BYTES), s, sin, sout, twW, rho_next, x_out, var.emit_v, C, H,
+                         bands, P, TT);
+        });
+      });
+      return true;
+    }
+  });
 }
 
 }  // namespace dpx
