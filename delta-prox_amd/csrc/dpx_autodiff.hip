@@ -692,7 +692,6 @@ extern "C" size_t dpx_admm_bwd_ws_bytes(int B, int C, int H, int W) {
 
 namespace dpx {
 int ad_partial_blocks(int C, int H, int W) { return ad_blocks((long)C * H * W); }
-// the stage kernels of the unrolled backward pass without their finishing launches: partial sums [rows][nblk] into `part`
 int zupdate_bwd_partials(float* gx, const dpx_bwd_term* terms, int nterms, float* part, int hist_bf16, int B, int C, int H, int W, hipStream_t s) {
   BwdPack T;
   T.n = nterms;
@@ -723,7 +722,6 @@ int solve_rhs_bwd_partials(const float* g, const float* x, const float* rhs, con
     DPX_LAUNCH("k_solve_rhs_bwd", k_solve_rhs_bwd, dim3(ad_blocks((long)C * H * W), B), dim3(256), 0, s, g, x, rhs, rho, T, part_a, part_b, C, H, W);
   return launch_status("dpx_admm_unrolled_backward");
 }
-// glam == NULL: only the rho reductions; grho == NULL: only the lambda reductions; nblk: partial sums per row
 int finish_iter_n(const float* part_lam, const float* part_a, const float* part_b, float* glam, float* grho, const float* rho, int nterms, int B,
                   int nblk, hipStream_t s) {
   const int nB = glam ? nterms * B : 0, nR = grho ? B : 0;
@@ -740,7 +738,6 @@ int finish_iter(const float* part_lam, const float* part_a, const float* part_b,
                 int C, int H, int W, hipStream_t s) {
   return finish_iter_n(part_lam, part_a, part_b, glam, grho, rho, nterms, B, ad_blocks((long)C * H * W), s);
 }
-// rhs stage of iteration `it` + z stage of iteration `it - 1` (k_rhs_z_bwd4); false: the planes do not fit it (W % 4)
 bool rhs_z_bwd_fused(const float* g, const float* x, const float* rhs, const float* rho, const dpx_bwd_term* terms, int nterms, const float* const* a_in,
                      float* const* a_out, float* gx, float* part_a, float* part_b, float* part_lam, int hist_bf16, int B, int C, int H, int W,
                      hipStream_t s, unsigned* counter, float* glam, float* grho) {
@@ -791,10 +788,9 @@ extern "C" int dpx_admm_solve_rho_grad(const float* g_rhs, const float* x, const
   return launch_status("dpx_admm_solve_rho_grad");
 }
 
-namespace dpx {
 // dpx_admm_rhs_bwd with the two sums that follow it in the unrolled backward pass folded in: gu[i] = gu_add[i] - gv[i] and
 // grho = <g, rhs> / rho + grho_add (both additions nullable)
-int rhs_bwd_impl(const float* g, const float* rhs, const float* rho, const int* linops, int nterms, float* const* gv, float* const* gu,
+static int rhs_bwd_impl(const float* g, const float* rhs, const float* rho, const int* linops, int nterms, float* const* gv, float* const* gu,
                  const float* const* gu_add, float* grho, const float* grho_add, int hist_bf16, int B, int C, int H, int W, void* ws, hipStream_t s) {
   RhsBwdPack T;
   T.n = nterms;
@@ -811,7 +807,6 @@ int rhs_bwd_impl(const float* g, const float* rhs, const float* rho, const int* 
     DPX_LAUNCH("k_ad_finish", k_ad_finish, dim3(B), dim3(256), 0, s, (const float*)ws, grho, nblk, rho, grho_add);
   return launch_status("dpx_admm_rhs_bwd");
 }
-}  // namespace dpx
 
 extern "C" int dpx_admm_rhs_bwd(const float* g, const float* rhs, const float* rho, const int* linops, int nterms, float* const* gv,
                                 float* const* gu, float* grho, int B, int C, int H, int W, void* ws, dpx_stream_t stream) {

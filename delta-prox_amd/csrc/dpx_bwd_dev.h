@@ -65,9 +65,4 @@ __device__ __forceinline__ float bwd_wave_sum(float v) {
   return v;
 }
 
-// dpx_bwd_rows_par.hip: own rows per workgroup of the row-parallel kernel (0: the plane is not taken) and its launch
-int bwd_rows_par_own(int P, int H, int W);
-int bwd_rows_par_launch(const float2* sin, float2* sout, const BwdRowTerms& TT, const float* rho, float* part_a, float* part_b, float* part_lam, int B,
-                        int C, int H, int W, int bands, const float2* twW, hipStream_t s);
-
 }  // namespace dpx

@@ -308,7 +308,6 @@ static int bwd_rows_band(int H, int W) {
   return R > H ? H : R;
 }
 
-// workgroups (= partial-sum slots) per image of the launch below; 0: planes this kernel does not take
 int bwd_rows_slots(int B, int C, int H, int W, int max_slots) {
   if (!(W == 256 || W == 512 || W == 1024) || !pow2_path_available(H, W) || H % 16) return 0;
   const int own = bwd_rows_par_own(B * C, H, W);       // > 0: the row-parallel kernel (dpx_bwd_rows_par.hip) takes the launch
@@ -316,8 +315,6 @@ int bwd_rows_slots(int B, int C, int H, int W, int max_slots) {
   return C * bands <= max_slots ? C * bands : 0;
 }
 
-// One backward iteration's row half.  spec_in: the column kernel's output (g_rhs^ of iteration t); spec_out: the row transform of g_x.
-// x / rhs: history of iteration t; terms[i].v / lam: iteration t - 1; partial sums as bwd_rows_slots(...) slots per image.
 int bwd_rows_fused(const void* spec_in, void* spec_out, const float* x, const float* rhs, const float* rho, const dpx_bwd_term* terms, int nterms,
                    const float* const* a_in, float* const* a_out, float* g_out, int g_acc, float* part_a, float* part_b, float* part_lam, int hist_bf16, int B,
                    int C, int H, int W, const void* table, hipStream_t s) {

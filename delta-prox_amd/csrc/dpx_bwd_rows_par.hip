@@ -357,8 +357,6 @@ __global__ void __launch_bounds__(64 * NW, 4) k_bwd_rows_par(const float2* __res
 #endif
 constexpr int BWD_PAR_NW = DPX_BWD_PAR_NW;
 
-// own rows per workgroup (0: the lock-step kernel keeps the launch): launches of up to `unroll_bwd_par_max_rows` rows (planes x H; the
-// library's rule: 12288 -- config 5's twelve 512-row planes in one round of 16-wave workgroups), knob < 0 = never
 int bwd_rows_par_own(int P, int H, int W) {
   if (!(W == 256 || W == 512 || W == 1024)) return 0;      // (so rows_wave_lanes(W) below is 16, 32 or 64)
   const int knob = tune(TUNE_UNROLL_BWD_PAR_MAX_ROWS);

@@ -121,16 +121,6 @@ __global__ void k_square(float* __restrict__ out, const float* __restrict__ w, l
 
 using namespace dpx;
 
-namespace dpx {
-int masked_normal_apply(const float* p, float* Ap, float2* z, const float* mask2, int mask_images, const float* rho, float c, const int* done,
-                        int B, int H, int W, const void* table, hipStream_t s);     // dpx_fft.hip
-int masked_normal_apply_fused(float* p, const float* r, float* Ap, float2* z, const float* mask, int mask_images, const float* rho, float c,
-                              float* state, float* dotws, unsigned* counter, int B, int H, int W, const void* table, hipStream_t s);
-size_t masked_normal_fused_ws_floats(int B, int H, int W);
-int gram_test_fused(float* r, float* G, void* state, int B, long n_per_batch, void* ws, unsigned* counter, float init_rtol, float* x, const float* p,
-                    const float* Ap, int* host_flags, int host_tag, hipStream_t s);   // dpx_elementwise.hip
-}
-
 extern "C" size_t dpx_cg_state_bytes(int B) { return B > 0 ? (size_t)(5 * B + 4) * sizeof(float) : 0; }
 
 extern "C" int dpx_cg_init(void* state, const float* bnorm2, float rtol, int B, dpx_stream_t stream) {
@@ -188,7 +178,6 @@ extern "C" int dpx_zero(void* p, size_t bytes, dpx_stream_t stream) {
 // ws (dpx_cg_masked_fft_ws_bytes): r, p, Ap [B n] floats; two complex [B n] buffers (the second one unused since the operator
 // became three fused launches); mask^2; state; Gram; dot workspace.
 // ---------------------------------------------------------------------------------------------------------------------
-namespace dpx { bool masked_normal_fits(int H, int W); }
 // 1 when dpx_cg_masked_fft takes this batch of planes (B <= 64 images, planes within its LDS-resident transforms): callers fall
 // back to the generic cg() loop on the same primitives otherwise
 extern "C" int dpx_cg_masked_fft_supported(int B, int H, int W) { return B >= 1 && B <= 64 && H > 0 && W > 0 && dpx::masked_normal_fits(H, W) ? 1 : 0; }

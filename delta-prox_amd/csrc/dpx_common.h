@@ -314,7 +314,6 @@ struct Plan1D {
   int nf;
   int radix[20];
 };
-Plan1D make_plan(int n);
 
 // half-spectrum geometry of an H x W real plane: Ws stored columns; for even W the Nyquist column
 // is packed into the imaginary part of column 0 (both are real-valued after the row transform).
@@ -357,9 +356,6 @@ struct SpecArgs {
   float scale;         // 1/(H*W)
 };
 
-int spectral_apply(const float* x, float* y, int op, const SpecArgs& a, int B, int C, int H, int W,
-                   const void* table, void* ws, hipStream_t stream);
-
 // Stencil passes: the hardware deals workgroup i to XCD i % 8, so neighbouring rows of a plane -- handled by neighbouring workgroups --
 // land in eight different L2s and every halo row crosses the fabric again (k_zupdate_rhs, 8 x 3 x 1000 x 1000, FETCH_SIZE: 582 MB for 288 MB
 // of operands = x thrice, u_0 twice).  xcd_block() renumbers the workgroups of a launch whose size is a multiple of 8 so that every XCD
@@ -382,3 +378,5 @@ static inline int grid_for(long n, int block, int cap = 256 * 8) {
 }
 
 }  // namespace dpx
+
+#include "dpx_internal.h"   // the functions one .hip file defines and another calls

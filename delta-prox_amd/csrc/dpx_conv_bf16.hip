@@ -749,13 +749,7 @@ __global__ void k_pnp_tail(const float* __restrict__ o, PnpTail Q, int B, int C,
 }
 
 static int ffdnet_forward_bf16_impl(const float* x, float* y, const float* sigma, const void* packed, int in_nc, int nc, int nb, int mode, int B, int H,
-                                    int W, void* ws, dpx_stream_t stream, const PnpTail* tail, bool packed_in = false);
-extern "C" int dpx_ffdnet_forward_bf16(const float* x, float* y, const float* sigma, const void* packed, int in_nc, int nc, int nb, int mode,
-                                       int B, int H, int W, void* ws, dpx_stream_t stream) {
-  return ffdnet_forward_bf16_impl(x, y, sigma, packed, in_nc, nc, nb, mode, B, H, W, ws, stream, nullptr);
-}
-static int ffdnet_forward_bf16_impl(const float* x, float* y, const float* sigma, const void* packed, int in_nc, int nc, int nb, int mode, int B, int H,
-                                    int W, void* ws, dpx_stream_t stream, const PnpTail* tail, bool packed_in) {
+                                    int W, void* ws, dpx_stream_t stream, const PnpTail* tail, bool packed_in = false) {
   DPX_REQUIRE(x && y && sigma && packed && ws, "dpx_ffdnet_forward_bf16: null pointer");
   DPX_REQUIRE(B > 0 && H > 0 && W > 0 && in_nc > 0 && nb >= 2 && nc % 16 == 0 && nc <= 96 && 4 * in_nc <= 96 &&
                   (mode == 6 || mode == 1 || mode == 3 || mode == 4),
@@ -802,6 +796,10 @@ static int ffdnet_forward_bf16_impl(const float* x, float* y, const float* sigma
     DPX_LAUNCH("k_bx_unpack_out", k_bx_unpack_out, dim3(grid_for((long)B * in_nc * H * W, 256, 8192)), dim3(256), 0, s, last, y, B, in_nc, H, W, H2,
                W2, GL);
   return launch_status("dpx_ffdnet_forward_bf16");
+}
+extern "C" int dpx_ffdnet_forward_bf16(const float* x, float* y, const float* sigma, const void* packed, int in_nc, int nc, int nb, int mode,
+                                       int B, int H, int W, void* ws, dpx_stream_t stream) {
+  return ffdnet_forward_bf16_impl(x, y, sigma, packed, in_nc, nc, nb, mode, B, H, W, ws, stream, nullptr);
 }
 
 // ---- reverse mode on the split kernels (frozen weights: gradients w.r.t. the image and sigma; the reference differentiates
@@ -944,12 +942,6 @@ extern "C" int dpx_ffdnet_backward_bf16(const float* gy, float* gx, float* gsigm
 // Forward and backward-data stay on the split kernels (C8 planes); the weight-gradient GEMM of a layer reads the same planes -- the gradient
 // w.r.t. its pre-activation output and its saved input -- in the arithmetic of the backward pass (k_wgrad_c8, dpx_wgrad_c8.hip).  (Round 4 fed
 // planar copies of both operands to a register kernel, k_wgrad_bf16x3: 338 us per 96 -> 96 layer at 2 x 384 x 384 against 157 now.)
-namespace dpx {
-size_t wgrad_c8_ws_floats(int cout_max, int cin_max);                // dpx_wgrad_c8.hip
-void launch_wgrad_c8(int mode, const float* G, const float* A, float* gw, float* gb, int Cout, int Cin_w, int Gg, int Ga, int B, int H, int W,
-                     float* ws, const float* mul, hipStream_t s);
-}
-
 extern "C" size_t dpx_ffdnet_bf16_bwd_w_ws_bytes(int B, int in_nc, int nc, int H, int W) {
   return dpx_ffdnet_bf16_bwd_ws_bytes(B, in_nc, nc, H, W) +
          wgrad_c8_ws_floats(nc > 4 * in_nc ? nc : 4 * in_nc, nc > 4 * in_nc + 1 ? nc : 4 * in_nc + 1) * sizeof(float);

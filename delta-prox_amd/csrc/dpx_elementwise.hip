@@ -1122,8 +1122,6 @@ extern "C" int dpx_bdot(const float* x, const float* y, float* out, int B, long 
 }
 
 namespace dpx {
-// Gram pass + finish + stop rule in one launch (dpx_cg_masked_fft's fused iteration, B <= 32); ws: B * B * gram_blocks floats
-// x / p / Ap non-null: the pending update x += alpha p, r -= alpha A p of the previous iteration is applied on the way (r is written)
 int gram_test_fused(float* r, float* G, void* state, int B, long n_per_batch, void* ws, unsigned* counter, float init_rtol, float* x, const float* p,
                     const float* Ap, int* host_flags, int host_tag, hipStream_t s) {
   int nblk = gram_blocks(n_per_batch);

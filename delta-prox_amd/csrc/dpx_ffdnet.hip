@@ -648,20 +648,6 @@ static void launch_wgrad(const float* G, const float* A, float* gw, float* gb, i
   }
 }
 
-// (for the split-arithmetic stack's training variant, dpx_conv_bf16.hip: the same weight-gradient kernels on planar copies of its C8 planes)
-namespace dpx {
-size_t ffd_wgrad_ws_floats(int nc, int in_nc) { return wgrad_ws_floats(nc, in_nc); }
-void ffd_launch_wgrad(const float* G, const float* A, float* gw, float* gb, int Cout, int Cin_w, int Cin_a, int B, int H2, int W2, float* ws,
-                      hipStream_t s) {
-  launch_wgrad(G, A, gw, gb, Cout, Cin_w, Cin_a, B, H2, W2, ws, s);
-}
-void ffd_launch_wgrad_reduce(const float* part, const float* part_b, float* gw, float* gb, int NG, int CoN, int co0, int Cin, int CoP, int CiP,
-                             const float* mul, hipStream_t s) {
-  DPX_LAUNCH("k_wgrad_reduce", k_wgrad_reduce, dim3(grid_for((long)CoN * Cin * 9 + CoN, 256, 1024)), dim3(256), 0, s, part, part_b, gw, gb, NG, CoN, co0,
-             Cin, CoP, CiP, 9, mul);
-}
-}  // namespace dpx
-
 // ---- training variants: forward that keeps every layer's output, backward-data through the whole stack ----------------
 extern "C" size_t dpx_ffdnet_acts_bytes(int B, int in_nc, int nc, int nb, int H, int W) {
   const size_t H2 = (H + 1) / 2, W2 = (W + 1) / 2, px = (size_t)B * H2 * W2;

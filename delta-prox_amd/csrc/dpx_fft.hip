@@ -20,7 +20,7 @@ namespace dpx {
 // ---------------------------------------------------------------------------------------------
 // plans and tables
 // ---------------------------------------------------------------------------------------------
-Plan1D make_plan(int n) {
+static Plan1D make_plan(int n) {
   Plan1D p;
   p.n = n;
   p.nf = 0;
@@ -1497,9 +1497,6 @@ static int masked_normal_apply_wave(float* p, const float* r, const float* beta,
 // ---------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------
-size_t pow2_spec_elems(int P, int H, int W);
-int spectral_apply_pow2(const float* x, float* y, int op, const SpecArgs& a, int B, int C, int H, int W,
-                        const void* table, void* ws, hipStream_t stream);
 
 static int rows_per_block(int M) {
   int r = 4096 / (M + 1);
@@ -1568,7 +1565,7 @@ static void launch_cols_il(int op, int ct, float2* spec, const SpecArgs& A, int 
   else launch_cols_il_o<4, 512>(op, spec, A, P, C, H, W, pcol, twH, s);
 }
 
-int spectral_apply(const float* x, float* y, int op, const SpecArgs& A, int B, int C, int H, int W,
+static int spectral_apply(const float* x, float* y, int op, const SpecArgs& A, int B, int C, int H, int W,
                    const void* table, void* ws, hipStream_t stream) {
   if (pow2_path_available(H, W)) return spectral_apply_pow2(x, y, op, A, B, C, H, W, table, ws, stream);
   const int P = B * C, Ws = spec_cols(W);
@@ -1630,7 +1627,6 @@ bool masked_normal_fits(int H, int W) {
   return (size_t)2 * rpb * (W + 1) * sizeof(float2) <= 64 * 1024 && (size_t)2 * CT * (H + 1) * sizeof(float2) <= 64 * 1024;
 }
 
-// z: one complex [B][H][W] scratch plane set.  Returns DPX_ERR_UNSUPPORTED for planes beyond the LDS-resident transform.
 int masked_normal_apply(const float* p, float* Ap, float2* z, const float* mask2, int mask_images, const float* rho, float c, const int* done,
                         int B, int H, int W, const void* table, hipStream_t s) {
   if (H == W && tune(TUNE_CG_WAVE_FFT) != 2) {         // (as in the fused iteration below)
@@ -1683,9 +1679,6 @@ static int fused_ct(int B, int H, int W) {
 }
 size_t masked_normal_fused_ws_floats(int B, int H, int W) { return (size_t)B * H + 8; }      // (one partial per workgroup; at most one workgroup per row)
 
-// The matvec of dpx_cg_masked_fft's fused iteration: the three launches above with the CG direction update in front (p = r + beta p
-// formed in the first kernel's load) and <p, Ap> behind (partial sums in the last kernel's store, finished by its last workgroup
-// into the CG state).  `mask` is the mask itself (squared on the fly).  dotws: masked_normal_fused_ws_floats floats.
 int masked_normal_apply_fused(float* p, const float* r, float* Ap, float2* z, const float* mask, int mask_images, const float* rho, float c,
                               float* state, float* dotws, unsigned* counter, int B, int H, int W, const void* table, hipStream_t s) {
   // 320 x 320 / 384 x 384 planes: every transform on one wave's registers (knob cg_wave_fft = 2 keeps the size-generic kernels)

@@ -849,8 +849,6 @@ static void cols_dispatch(int H, const float2* spec, float2* spec_out, const Spe
   }
 }
 
-bool seed_rows_seq_pow2(const int* linops, int n, const float* rho, const float* x0, float2* spec, int P, int C, int H, int W, const void* table,
-                        hipStream_t s);
 int seed_rows_pow2(const dpx_term* terms, int nterms, const float* rho, const float* x0, float2* spec, int B, int C, int H, int W, const void* table,
                    hipStream_t stream) {
   SeedTerms S_{};
@@ -910,11 +908,7 @@ int spectral_apply_pow2(const float* x, float* y, int op, const SpecArgs& A, int
   return launch_status("spectral_apply_pow2");
 }
 
-
-bool pgd_rows_seq_pow2(const float2* sin, float2* sout, float* x, const float* ktb, const float* rho, const float* lam, float alpha, int prox, int P,
-                       int C, int H, int W, const void* table, hipStream_t s);        // dpx_iter.hip: the streaming row pass
-
-int pgd_run_pow2(float* x, const float* ktb, const void* gram_otf, int prox, float alpha, const float* rho_tab, const float* lam_tab, int T,
+static int pgd_run_pow2(float* x, const float* ktb, const void* gram_otf, int prox, float alpha, const float* rho_tab, const float* lam_tab, int T,
                  int B, int C, int H, int W, const void* table, void* ws, hipStream_t stream) {
   const int P = B * C, Ws = W / 2;
   float2* spec = (float2*)ws;

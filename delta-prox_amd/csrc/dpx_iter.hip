@@ -761,9 +761,10 @@ __global__ void __launch_bounds__(256, 2) k_pgd_rows_seq(const float2* __restric
 }
 
 // run-time overrides shared with the ADMM row kernels (dpx_admm_iter_config): rows_mode 2 keeps the plain kernels, bands_per_plane > 0
-// fixes the band count
-extern int g_rows_mode_pgd, g_rows_band_pgd, g_chain_share;
-// false: the plane / batch does not fit the streaming kernel (the caller keeps k_pgd_rows, which serves every plane)
+// fixes the band count.  g_chain_share (dpx_admm_iter_share): sub-batches of one solve running as independent chains on separate streams
+// (dprox/algo/fused.py) share the GPU -- the row kernels size their bands for `chains` x the planes of one call.  A tuning hint only:
+// results do not depend on the band partition.
+static int g_rows_mode_pgd = 0, g_rows_band_pgd = 0, g_chain_share = 1;
 bool pgd_rows_seq_pow2(const float2* sin, float2* sout, float* x, const float* ktb, const float* rho, const float* lam, float alpha, int prox, int P,
                        int C, int H, int W, const void* table, hipStream_t s) {
   if (g_rows_mode_pgd == 2) return false;
@@ -935,7 +936,6 @@ __global__ void __launch_bounds__(256, 2) k_seed_rows_seq(SeedOps SO, const floa
   }
 }
 
-// false: the plane / batch does not fit the streaming kernel (the caller keeps k_seed_rows<FRESH>)
 bool seed_rows_seq_pow2(const int* linops, int n, const float* rho, const float* x0, float2* spec, int P, int C, int H, int W, const void* table,
                         hipStream_t s) {
   if (g_rows_mode_pgd == 2) return false;                 // (dpx_admm_iter_config: 2 = the plain kernels)
@@ -997,20 +997,9 @@ static bool launch_iter_rows(int W, const float2* sin, float2* sout, const IterT
   });
 }
 
-size_t pow2_spec_elems(int P, int H, int W);
-int cols_solve_pow2(const float2* spec_in, float2* spec_out, const SpecArgs& A, int P, int C, int H, int W, const void* table,
-                    hipStream_t stream);
-int rows_r2c_pow2(const float* x, float2* spec, int P, int H, int W, const void* table, hipStream_t stream);
-int seed_rows_pow2(const dpx_term* terms, int nterms, const float* rho, const float* x0, float2* spec, int B, int C, int H, int W, const void* table,
-                   hipStream_t stream);
-
 }  // namespace dpx
 
 using namespace dpx;
-namespace dpx {
-int iter_rows_impl(const void* spec_in, void* spec_out, const dpx_term* terms, int nterms, const float* rho_next, float* x_out, int emit_v,
-                   float* rhs_out, int emit_bf16, int B, int C, int H, int W, const void* table, dpx_stream_t stream);
-}
 
 static int terms_ok(const dpx_term* terms, int nterms) {
   if (nterms < 1 || nterms > DPX_MAX_TERMS || !terms) return 0;
@@ -1027,19 +1016,16 @@ static int terms_ok(const dpx_term* terms, int nterms) {
 // ring-buffer kernel; bands_per_plane 0 = automatic.  The environment variables DPX_ITER_ROWS / DPX_ITER_BAND set the defaults.
 enum RowsMode { ROWS_AUTO = 0, ROWS_SEQ = 1, ROWS_LOCKSTEP = 2, ROWS_PAR = 3 };      // dpx_admm_iter_config's rows_mode / the iter_rows knob
 static int g_rows_mode = -1, g_rows_band = -1;
-namespace dpx { int g_rows_mode_pgd = 0, g_rows_band_pgd = 0, g_chain_share = 1; int iter_seq_bands(int P, int H, int W, int forced); }
-// Sub-batches of one solve running as independent chains on separate streams (dprox/algo/fused.py) share the GPU: the row kernels size
-// their bands for `chains` x the planes of one call.  A tuning hint only -- results do not depend on the band partition.
 // Bands per plane of the streaming row kernel (k_iter_rows_seq) for a launch of P planes of H x W: as many as keep every T-lane group
 // of the launch resident at once (2 workgroups of 4 waves per CU, times the chains that share the GPU), rounded UP to a power of two
 // (H is one: bands of equal length keep the waves of a workgroup in step, and ~1.5 rounds of resident groups beat one round of
 // unequal bands -- 8x3x1024^2: 128 bands of 8 rows 106 us, 85 bands of 12-13 rows 109 us, 96 / 102 / 136 bands 127-133 us), at least
 // `iter_band_min_rows` (4) rows long, and such that the groups fill whole workgroups.  A partition always exists: if no count below
 // the rule's fills whole workgroups (P odd and large), the smallest count that does is taken (per_block / gcd(P, per_block) <= 16).
-int dpx::iter_seq_bands(int P, int H, int W, int forced) {
+static int iter_seq_bands(int P, int H, int W, int forced) {
   const int per_block = seq_groups_per_block(W);
   if (!per_block) return 0;                              // (no streaming kernel for W: no partition)
-  int nb = resident_bands_pow2(per_block / 4, P, dpx::g_chain_share);
+  int nb = resident_bands_pow2(per_block / 4, P, g_chain_share);
   if (forced) nb = forced;
   const int min_rows_knob = tune(TUNE_ITER_BAND_MIN_ROWS);
   const int min_rows = min_rows_knob > 0 ? min_rows_knob : 4;
@@ -1059,19 +1045,19 @@ int dpx::iter_seq_bands(int P, int H, int W, int forced) {
 
 extern "C" int dpx_admm_iter_bands(int planes, int H, int W) {
   if (planes < 1 || H < 16 || !(W == 256 || W == 512 || W == 768 || W == 1024)) return 0;
-  return dpx::iter_seq_bands(planes, H, W, g_rows_band > 0 ? g_rows_band : tune(TUNE_ITER_BAND));
+  return iter_seq_bands(planes, H, W, g_rows_band > 0 ? g_rows_band : tune(TUNE_ITER_BAND));
 }
 extern "C" int dpx_admm_iter_share(int chains) {
   DPX_REQUIRE(chains >= 1 && chains <= 16, "dpx_admm_iter_share: chains must be in [1, 16]");
-  dpx::g_chain_share = chains;
+  g_chain_share = chains;
   return DPX_OK;
 }
 extern "C" int dpx_admm_iter_config(int rows_mode, int bands_per_plane) {
   DPX_REQUIRE(rows_mode >= 0 && rows_mode <= 3 && bands_per_plane >= 0, "dpx_admm_iter_config: bad arguments");
   g_rows_mode = rows_mode;
   g_rows_band = bands_per_plane;
-  dpx::g_rows_mode_pgd = rows_mode;                      // (dpx_pgd_run's row pass follows the same switch: 2 = the plain kernel)
-  dpx::g_rows_band_pgd = bands_per_plane;
+  g_rows_mode_pgd = rows_mode;                      // (dpx_pgd_run's row pass follows the same switch: 2 = the plain kernel)
+  g_rows_band_pgd = bands_per_plane;
   return DPX_OK;
 }
 
@@ -1126,8 +1112,6 @@ extern "C" int dpx_admm_iter_rows(const void* spec_in, void* spec_out, const dpx
   return dpx::iter_rows_impl(spec_in, spec_out, terms, nterms, rho_next, x_out, emit_v, nullptr, 0, B, C, H, W, table, stream);
 }
 
-// + rhs_out (nullable): the right-hand-side increment handed to the next x-update, also written as an image;
-// + emit_bf16: x_out, terms[i].v and rhs_out are bf16 planes (written with round-to-nearest-even)
 int dpx::iter_rows_impl(const void* spec_in, void* spec_out, const dpx_term* terms, int nterms, const float* rho_next, float* x_out, int emit_v,
                         float* rhs_out, int emit_bf16, int B, int C, int H, int W, const void* table, dpx_stream_t stream) {
   DPX_REQUIRE(spec_in && table && (spec_out || !rho_next), "dpx_admm_iter_rows: null pointer");
@@ -1166,7 +1150,7 @@ int dpx::iter_rows_impl(const void* spec_in, void* spec_out, const dpx_term* ter
   //  sooner there than the streaming kernel's sequential ones; measured crossover between 256- and 512-wide planes)
   const bool tiny = W <= 256 && (long)P * H <= 4096 && mode != ROWS_SEQ;
   if ((mode != ROWS_LOCKSTEP && W <= 1024 && !tiny) || W == 768) {      // (768-wide rows exist on the streaming kernel only)
-    const int nb = dpx::iter_seq_bands(P, H, W, g_rows_band >= 0 ? g_rows_band : tune(TUNE_ITER_BAND));
+    const int nb = iter_seq_bands(P, H, W, g_rows_band >= 0 ? g_rows_band : tune(TUNE_ITER_BAND));
     if (nb >= 1 && (P * nb) % seq_groups_per_block(W) == 0) {      // (nb >= 1: W has a streaming kernel, seq_groups_per_block(W) > 0)
       if (!launch_iter_rows_seq(W, sin, sout, TT, rho_next, x_out, emit_v, C, H, nb, P, tw, s)) launch_fail("k_iter_rows_seq: no instantiation for %d-wide planes", W);
       return launch_status("dpx_admm_iter_rows");

@@ -95,8 +95,4 @@ template <class F> static inline void dispatch_iter_variant(const IterVariant& v
 #endif
 constexpr int R_LDX = DPX_R_LDX, R_LDU = DPX_R_LDU, R_STU = DPX_R_STU, R_STX = DPX_R_STX;
 
-// dpx_iter_par.hip: the row pass for launches of a few planes (false: not applicable -- the caller keeps the streaming kernel)
-bool launch_iter_rows_par(const float2* sin, float2* sout, const IterTerms& TT, const float* rho_next, float* x_out, int emit_v, int C, int H, int W,
-                          int P, const float2* twW, hipStream_t s, bool forced);
-
 }  // namespace dpx

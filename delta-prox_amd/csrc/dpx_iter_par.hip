@@ -353,8 +353,6 @@ __global__ void __launch_bounds__(64 * NW, 1) k_iter_rows_par(const float2* __re
   }
 }
 
-// Row-parallel kernel for launches that cannot fill the chip with band walkers: P * H rows up to `iter_par_max_rows` (knob; the
-// library's rule: 8192 rows of 1024 / 512 / 256 pixels -- 1 .. 2 rounds of one 16-wave workgroup per CU), or forced (iter_rows = 3).
 bool launch_iter_rows_par(const float2* sin, float2* sout, const IterTerms& TT, const float* rho_next, float* x_out, int emit_v, int C, int H, int W,
                           int P, const float2* twW, hipStream_t s, bool forced) {
   if (W != 1024 && W != 512 && W != 256) return false;

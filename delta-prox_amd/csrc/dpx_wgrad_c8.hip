@@ -8,8 +8,6 @@
 #include "dpx_wgrad_c8_dev.h"
 
 namespace dpx {
-unsigned* f16_overflow_flag();                                      // dpx_conv_bf16.hip
-
 // gw[co][ci][tap], gb[co] = the sums over the NG workgroups' partial slices, in a fixed order (the same bits run to run), times *mul.  A thread owns
 // one element of the kernel's tiled layout (consecutive threads read consecutive floats of every slice) and writes it where it belongs.
 __global__ void __launch_bounds__(256) k_wgrad_c8_reduce(const float* __restrict__ part, const float* __restrict__ part_b, float* __restrict__ gw,
@@ -81,8 +79,6 @@ static void launch_wc_mt(int mt, int nt, const float* G, const float* A, float* 
 #undef DPX_WC
 }
 
-// G: C8 [B][Gg][H][W][8], A: C8 [B][Ga][H][W][8]; gw: [Cout][Cin_w][9], gb: [Cout] (Cout <= 8 Gg, Cin_w <= 8 Ga, both <= 96);
-// mode 3: split-f16 (G scaled into the binary16 range by the caller), 6: split-bf16; mul (device, nullable): the sums leave multiplied by *mul
 void launch_wgrad_c8(int mode, const float* G, const float* A, float* gw, float* gb, int Cout, int Cin_w, int Gg, int Ga, int B, int H, int W,
                      float* ws, const float* mul, hipStream_t s) {
   const int MT = (Cout + 31) / 32, NT = (Cin_w + 31) / 32, CoP = MT * 32, CiP = NT * 32;

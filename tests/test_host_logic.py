@@ -90,6 +90,82 @@ def test_tuning_registry_is_documented_and_round_trips():
             assert all("kKnobs[i].env" in ln or "DPX_RCCL_LIB" in ln for ln in hits), (f, hits)
 
 
+def _strip_comments_and_strings(src):
+    """comments blanked and string / character literals emptied, line structure kept"""
+    pat = re.compile(r'//[^\n]*|/\*.*?\*/|"(?:\\.|[^"\\\n])*"|\'(?:\\.|[^\'\\\n])*\'', re.S)
+    return pat.sub(lambda m: m.group(0)[0] * 2 if m.group(0)[0] in "\"'" else re.sub(r"[^\n]", " ", m.group(0)), src)
+
+
+def _declarations(text):
+    """(line, name, statement) of every body-less function declaration at namespace scope of stripped source: a statement that starts in
+    column 0, has a parameter list closed by `);` and no `{`.  One-line `namespace x { ...; }` blocks count as their statements."""
+    text = re.sub(r"^namespace\b[^{\n]*\{([^{}\n]*)\}[ \t]*$", lambda m: "\n".join(s.strip() + ";" for s in m.group(1).split(";") if s.strip()),
+                  text, flags=re.M)               # (only ever met on lines the test then rejects, so the shifted line numbers do not matter)
+    for m in re.finditer(r"^(?![#}\s])([^;{}=]*?\([^;{}]*\))\s*;", text, re.M):
+        stmt = " ".join(m.group(1).split())
+        depth, i = 0, len(stmt) - 1
+        while i >= 0:                             # the parenthesis that opens the parameter list
+            depth += (stmt[i] == ")") - (stmt[i] == "(")
+            if depth == 0:
+                break
+            i -= 1
+        head = re.search(r"([A-Za-z_]\w*)\s*$", stmt[:i])
+        if not head or stmt.startswith(("typedef ", "using ")) or len(re.findall(r"[A-Za-z_]\w*", stmt[:i])) < 2:
+            continue                              # function-pointer / vector typedefs, static_assert(...), a macro call
+        yield text.count("\n", 0, m.start()) + 1, head.group(1), stmt, m.end()
+
+
+def _defined_at(name, text):
+    return re.findall(r"^(?![#}\s])[^;{}=()]*\b(?:dpx::)?%s\s*\([^;{}]*\)\s*\{" % re.escape(name), text, re.M)
+
+
+def _cross_file_declaration_faults(csrc):
+    """what test_cross_file_internals_are_declared_once_in_dpx_internal_h rejects in a csrc/ directory, one line each"""
+    hips = {f: _strip_comments_and_strings(open(os.path.join(csrc, f)).read()) for f in sorted(os.listdir(csrc)) if f.endswith(".hip")}
+    faults = []
+    for f, text in hips.items():
+        for line, name, stmt, end in _declarations(text):
+            forward = ("__global__" in stmt or stmt.startswith("template")) and _defined_at(name, text[end:])
+            if not forward:
+                faults.append(f"{f}:{line}: prototype of {name} outside dpx_internal.h: {stmt[:100]}")
+        for m in re.finditer(r"\bextern\b(?!\s*\"\"|\s+__shared__)", text):
+            line = text.count("\n", 0, m.start()) + 1
+            faults.append(f"{f}:{line}: extern: {text.splitlines()[line - 1].strip()[:100]}")
+    hdr = os.path.join(csrc, "dpx_internal.h")
+    if not os.path.exists(hdr):
+        return faults + ["dpx_internal.h is missing"]
+    if '#include "dpx_internal.h"' not in open(os.path.join(csrc, "dpx_common.h")).read():
+        faults.append("dpx_common.h does not include dpx_internal.h")
+    names = [name for _, name, _, _ in _declarations(_strip_comments_and_strings(open(hdr).read()))]
+    if len(names) < 20 or len(set(names)) != len(names):
+        faults.append(f"dpx_internal.h: {len(names)} declarations, {len(set(names))} names")
+    for name in names:
+        defs = [(f, d) for f, text in hips.items() for d in _defined_at(name, text)]
+        users = [f for f, text in hips.items() if re.search(r"\b%s\s*\(" % re.escape(name), text)]
+        if len(defs) != 1 or defs[0][1].startswith("static"):
+            faults.append(f"dpx_internal.h: {name} has {len(defs)} non-static definitions in csrc/*.hip: {[f for f, _ in defs]}")
+        elif len(users) < 2:
+            faults.append(f"dpx_internal.h: {name} is used by {defs[0][0]} alone: make it static there")
+    return faults
+
+
+def test_cross_file_internals_are_declared_once_in_dpx_internal_h():
+    """A function of one .hip file that another one calls is declared in csrc/dpx_internal.h (which dpx_common.h includes, so the defining
+    file sees it too and the compiler checks the definition against it) and nowhere else: no .hip file holds a body-less declaration at
+    namespace scope -- except a forward declaration of a kernel or a template it defines further down -- or an `extern` other than
+    extern "C" / extern __shared__, and every name the header declares has exactly one definition and a user in another file."""
+    probe = _strip_comments_and_strings(
+        'namespace dpx {\nint far_away(const float* x, int n,\n            bool flag = false);   // dpx_other.hip\n'
+        'template <int N> __global__ void k_later(float* p);\n__global__ void k_never(float* p);\nstatic int g = f(3);\n'
+        'typedef void (*Fn)(int);\nint here(int n) { return n; }\ntemplate <int N> __global__ void k_later(float* p) { p[0] = N; }\n}\n'
+        'namespace dpx { int g_a = 0; bool one_liner(int H); }\n')
+    found = [(name, ("__global__" in stmt or stmt.startswith("template")) and bool(_defined_at(name, probe[end:])))
+             for _, name, stmt, end in _declarations(probe)]
+    assert found == [("far_away", False), ("k_later", True), ("k_never", False), ("one_liner", False)], found
+    faults = _cross_file_declaration_faults(os.path.join(ROOT, "delta-prox_amd", "csrc"))
+    assert not faults, "\n".join(faults)
+
+
 def test_wheel_builds_and_imports_without_path_edits(tmp_path):
     """packaging (pyproject.toml + setup.py): `pip wheel` runs the HIP build hook, the wheel holds the package `dprox` with
     dprox/lib/libdpx_hip.so inside, and a fresh interpreter imports it from the unpacked wheel alone (no sys.path edits, no repo)"""
