@@ -398,6 +398,51 @@ def bgram(r):
     return out
 
 
+ANDERSON_MAX_M = 8
+
+
+class AndersonHistory:
+    """The piece-major history of an Anderson solve (dpx_anderson_gram_row / dpx_anderson_mix): ``F`` and ``G = F - X`` are
+    [m, P, B, *piece] (m slots of P pieces; ``F[slot, p]`` is a contiguous image stack an iteration kernel writes directly), ``X``
+    [P, B, *piece] is the point the next evaluation of f starts from, ``Hm`` [B, m, m] the Gram matrices kept across steps."""
+
+    def __init__(self, m, P, B, piece_shape, device):
+        if not 1 <= int(m) <= ANDERSON_MAX_M:
+            raise be.DpxError(f"anderson: history of m={m} slots (1 .. {ANDERSON_MAX_M})")
+        if not be.host_mode() and torch.device(device).type != "cuda":
+            raise be.DpxError(f"anderson history on {device}: the MI355X backend only runs on HIP devices (no CPU fallback)")
+        self.m, self.P, self.B = int(m), int(P), int(B)
+        piece_shape = tuple(int(s) for s in piece_shape)
+        self.D = int(np.prod(piece_shape))
+        if self.P < 1 or self.B < 1 or self.D < 1:
+            raise be.DpxError(f"anderson: empty state (P={P}, B={B}, piece {piece_shape})")
+        f32 = dict(dtype=torch.float32, device=device)
+        self.F = torch.empty((self.m, self.P, self.B) + piece_shape, **f32)
+        self.G = torch.empty_like(self.F)
+        self.X = torch.empty((self.P, self.B) + piece_shape, **f32)
+        self.Hm = torch.zeros(self.B, self.m, self.m, **f32)
+        self.nrm = torch.zeros(self.B, 2, **f32)
+        self._alpha = torch.zeros(self.B * self.m, **f32)
+        # (the reduction's tickets live at the head of the workspace and must start from zero: not the shared scratch of workspace())
+        self.ws = torch.zeros(max(be.lib().query("dpx_anderson_ws_bytes", self.B, self.P, self.D), 16), dtype=torch.uint8, device=device)
+
+    def gram_row(self, ks, n, X=None):
+        """after f(X) has been written into slot ``ks`` of F: G[ks] = F[ks] - X, row / column ks of Hm over the slots j < n, and
+        nrm[b] = (|G_ks|^2, |F_ks|^2).  ``X``: the point f was evaluated at when it is not ``self.X`` (another slot of F, say)"""
+        X = self.X if X is None else require(X, what="anderson point")
+        if X.numel() != self.X.numel():
+            raise be.DpxError(f"anderson: point of shape {tuple(X.shape)} for a state of shape {tuple(self.X.shape)}")
+        be.lib().call("dpx_anderson_gram_row", ptr(X), ptr(self.F), ptr(self.G), ptr(self.Hm), ptr(self.nrm), int(ks), int(n), self.m, self.P,
+                      self.B, self.D, ptr(self.ws), be.stream())
+        return self.nrm
+
+    def mix(self, n, beta=1.0, lam=1e-4):
+        """X = beta sum_i alpha_i F_i + (1 - beta) sum_i alpha_i X_i over the slots i < n; returns alpha [B, n]"""
+        be.lib().call("dpx_anderson_mix", ptr(self.F), ptr(self.G), ptr(self.Hm), ptr(self.X), ptr(self._alpha), int(n), self.m, c_float(beta),
+                      c_float(lam), self.P, self.B, self.D, be.stream())
+        return self._alpha[:self.B * int(n)].view(self.B, int(n))
+
+
 def cg_masked_fft(b, mask, rho, n_identity, rtol, max_iters):
     """the whole CG x-update of a masked-Fourier data term in one C call (dpx_cg_masked_fft); returns (x, exit iteration)"""
     require(b, what="cg right-hand side")

@@ -10,6 +10,7 @@ import torch.nn as nn
 from .. import _backend as be
 from ..linalg import LinearSolveConfig
 from ..proxfn import ProxFn
+from .deq import DEQSolver
 from .driver import Algorithm
 from .gradient import ProximalGradientDescent
 from .splitting import ADMM, HQS, ADMM_vxu, LinearizedADMM, PockChambolle
@@ -134,7 +135,7 @@ def build_unrolled_solver(solver, share=True, dtype="f32", **kwargs):
     return UnrolledSolver(solver, share=share, dtype=dtype, **kwargs)
 
 
-SPECAILIZATIONS = {"unroll": build_unrolled_solver}
+SPECAILIZATIONS = {"unroll": build_unrolled_solver, "deq": DEQSolver}
 
 
 def specialize(solver: Algorithm, method: str = "unroll", device: Union[str, torch.device] = "cuda", **kwargs):

@@ -706,6 +706,26 @@ int dpx_ffdnet_backward(const float* gy, float* gx, float* gsigma, float* const*
  * is never formed; the shifts are summed in a fixed order (bit-reproducible).                                                  */
 int dpx_nlm(const float* v, float* out, const float* sigma, int B, int C, int H, int W, int search, int patch, dpx_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------ */
+/* Anderson acceleration (DEQ specialization)                                                  */
+/* ------------------------------------------------------------------------------------------ */
+/* anderson -- specialization/deq/utils/solvers.py:193-254, on a piece-major history: F and G = F - X are [m][P][B][D] (m <= 8 slots of
+ * P pieces, each a contiguous [B][D] image stack), X and Xout are [P][B][D], Hm is [B][m][m] (the Gram matrices <G_i, G_j> per image,
+ * kept across steps, no ridge), nrm is [B][2].  All float32 on the device.  16-byte accesses when D % 4 == 0 and the buffers are
+ * 16-byte aligned, element-wise otherwise.
+ *   dpx_anderson_gram_row  after f has been evaluated into slot ks of F: writes slot ks of G = F - X, row and column ks of Hm against
+ *                          the slots j < n (ks < n <= m) and nrm[b] = (|G_ks|^2, |F_ks|^2).  One launch; the partial sums go through
+ *                          ws (dpx_anderson_ws_bytes; its first use must find it zero-filled, every call leaves its head zero again)
+ *                          and are added in a fixed order: no floating-point atomics, two calls give the same bits.
+ *   dpx_anderson_mix       per image: alpha = rows 1 .. n of the solution of [[0, 1^T], [1, Hm[:n,:n] + lam I]] [nu; alpha] = [1; 0]
+ *                          (float64, partial pivoting), written to alpha [B][n]; Xout = beta sum_i alpha_i F_i +
+ *                          (1 - beta) sum_i alpha_i (F_i - G_i) over the slots i < n.  One launch.                                    */
+size_t dpx_anderson_ws_bytes(int B, int P, long D);
+int dpx_anderson_gram_row(const float* X, const float* F, float* G, float* Hm, float* nrm, int ks, int n, int m, int P, int B, long D,
+                          void* ws, dpx_stream_t stream);
+int dpx_anderson_mix(const float* F, const float* G, const float* Hm, float* Xout, float* alpha, int n, int m, float beta, float lam,
+                     int P, int B, long D, dpx_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
