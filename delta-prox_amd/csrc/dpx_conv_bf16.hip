@@ -748,27 +748,29 @@ __global__ void k_pnp_tail(const float* __restrict__ o, PnpTail Q, int B, int C,
   }
 }
 
-static int ffdnet_forward_bf16_impl(const float* x, float* y, const float* sigma, const void* packed, int in_nc, int nc, int nb, int mode, int B, int H,
-                                    int W, void* ws, dpx_stream_t stream, const PnpTail* tail, bool packed_in = false) {
-  DPX_REQUIRE(x && y && sigma && packed && ws, "dpx_ffdnet_forward_bf16: null pointer");
+// The forward pass in `buf`: [packed input][hidden layers][last layer], all C8.  keep_all: every hidden layer's output stays, layer l's at slot l
+// (the training pass dpx_ffdnet_forward_bf16_save: modes 3 and 6, no ffdnet_presplit, no tail, no packed_in); otherwise the hidden layers
+// alternate between two slots.  `name`: the entry point, for its messages.
+static int ffdnet_forward_bf16_impl(const char* name, bool keep_all, const float* x, float* y, const float* sigma, const void* packed, int in_nc, int nc,
+                                    int nb, int mode, int B, int H, int W, void* buf, dpx_stream_t stream, const PnpTail* tail, bool packed_in = false) {
+  DPX_REQUIRE(x && y && sigma && packed && buf, "%s: null pointer", name);
   DPX_REQUIRE(B > 0 && H > 0 && W > 0 && in_nc > 0 && nb >= 2 && nc % 16 == 0 && nc <= 96 && 4 * in_nc <= 96 &&
-                  (mode == 6 || mode == 1 || mode == 3 || mode == 4),
-              "dpx_ffdnet_forward_bf16: unsupported configuration (in_nc=%d nc=%d nb=%d mode=%d)", in_nc, nc, nb, mode);
+                  (mode == 6 || mode == 3 || (!keep_all && (mode == 1 || mode == 4))),
+              "%s: unsupported configuration (in_nc=%d nc=%d nb=%d mode=%d)", name, in_nc, nc, nb, mode);
   hipStream_t s = (hipStream_t)stream;
   const int H2 = (H + 1) / 2, W2 = (W + 1) / 2;
-  DPX_REQUIRE((size_t)2 * H2 * W2 * 8 < ((size_t)1 << 32), "dpx_ffdnet_forward_bf16: plane %dx%d too large", H, W);
+  DPX_REQUIRE((size_t)2 * H2 * W2 * 8 < ((size_t)1 << 32), "%s: plane %dx%d too large", name, H, W);
   const size_t px = (size_t)B * H2 * W2;
   const int G0 = groups16(4 * in_nc + 1), Gc = groups16(nc), GL = groups16(4 * in_nc);
-  float* a0 = (float*)ws;
-  float* bufA = a0 + px * 8 * G0;
-  float* bufB = bufA + px * 8 * Gc;
-  float* last = bufB + px * 8 * Gc;
+  float* a0 = (float*)buf;
+  float* hidden = a0 + px * 8 * G0;
+  float* last = hidden + (size_t)(keep_all ? nb - 1 : 2) * px * 8 * Gc;
   // split-f16 inference with the activations travelling between the layers as pre-split operand planes (P8, bit-identical results): knob
   // ffdnet_presplit = 1, OFF by default.  Measured, round 4 (8x3x1024^2 colour / 32x1x320^2 gray, alternating runs on one box): 10.16 /
   // 3.00 ms with it, 9.93 - 10.14 / 2.85 ms without -- no split pass, no landing buffer and one barrier less per chunk buy nothing
   // (the kernel runs at the matrix pipe's power-limited rate), and two 8-byte stores per lane instead of one
   // 16-byte store in the epilogue cost a little.
-  const bool p8 = mode == 3 && tune(TUNE_FFDNET_PRESPLIT) == 1;
+  const bool p8 = !keep_all && mode == 3 && tune(TUNE_FFDNET_PRESPLIT) == 1;
   if (!packed_in)              // (packed_in: k_pnp_head has filled a0 -- plain C8, never with ffdnet_presplit)
     DPX_LAUNCH("k_bx_pack_in", k_bx_pack_in, dim3(grid_for((long)(px * 8 * G0), 256, 8192)), dim3(256), 0, s, x, sigma, a0, B, in_nc, H, W, H2, W2, G0,
                p8 ? 1 : 0);
@@ -778,7 +780,7 @@ static int ffdnet_forward_bf16_impl(const float* x, float* y, const float* sigma
   for (int l = 0; l < nb; ++l) {
     const int cin = bx_cin(l, in_nc, nc), cout = bx_cout(l, in_nc, nc, nb);
     const bool lastl = l == nb - 1;
-    float* dst = lastl ? last : ((l & 1) ? bufB : bufA);
+    float* dst = lastl ? last : hidden + (size_t)(keep_all ? l : (l & 1)) * px * 8 * Gc;
     const int gout = lastl ? GL : Gc;
     if (p8) launch_bx_p8_mt((cout + 31) / 32, !lastl, true, !lastl, cur, dst, wl, gin, gout, B, H2, W2, s);
     else if (bx_layer_is_wino(mode, l, cout)) launch_wino_mt((cout + 31) / 32, !lastl, cur, dst, wl, gin, gout, B, H2, W2, s);
@@ -795,11 +797,11 @@ static int ffdnet_forward_bf16_impl(const float* x, float* y, const float* sigma
   else
     DPX_LAUNCH("k_bx_unpack_out", k_bx_unpack_out, dim3(grid_for((long)B * in_nc * H * W, 256, 8192)), dim3(256), 0, s, last, y, B, in_nc, H, W, H2,
                W2, GL);
-  return launch_status("dpx_ffdnet_forward_bf16");
+  return launch_status(name);
 }
 extern "C" int dpx_ffdnet_forward_bf16(const float* x, float* y, const float* sigma, const void* packed, int in_nc, int nc, int nb, int mode,
                                        int B, int H, int W, void* ws, dpx_stream_t stream) {
-  return ffdnet_forward_bf16_impl(x, y, sigma, packed, in_nc, nc, nb, mode, B, H, W, ws, stream, nullptr);
+  return ffdnet_forward_bf16_impl("dpx_ffdnet_forward_bf16", false, x, y, sigma, packed, in_nc, nc, nb, mode, B, H, W, ws, stream, nullptr);
 }
 
 // ---- reverse mode on the split kernels (frozen weights: gradients w.r.t. the image and sigma; the reference differentiates
@@ -814,35 +816,7 @@ extern "C" size_t dpx_ffdnet_bf16_acts_bytes(int B, int in_nc, int nc, int nb, i
 
 extern "C" int dpx_ffdnet_forward_bf16_save(const float* x, float* y, const float* sigma, const void* packed, int in_nc, int nc, int nb, int mode,
                                             int B, int H, int W, void* acts, dpx_stream_t stream) {
-  DPX_REQUIRE(x && y && sigma && packed && acts, "dpx_ffdnet_forward_bf16_save: null pointer");
-  DPX_REQUIRE(B > 0 && H > 0 && W > 0 && in_nc > 0 && nb >= 2 && nc % 16 == 0 && nc <= 96 && 4 * in_nc <= 96 && (mode == 6 || mode == 3),
-              "dpx_ffdnet_forward_bf16_save: unsupported configuration (in_nc=%d nc=%d nb=%d mode=%d)", in_nc, nc, nb, mode);
-  hipStream_t s = (hipStream_t)stream;
-  const int H2 = (H + 1) / 2, W2 = (W + 1) / 2;
-  DPX_REQUIRE((size_t)2 * H2 * W2 * 8 < ((size_t)1 << 32), "dpx_ffdnet_forward_bf16_save: plane %dx%d too large", H, W);
-  const size_t px = (size_t)B * H2 * W2;
-  const int G0 = groups16(4 * in_nc + 1), Gc = groups16(nc), GL = groups16(4 * in_nc);
-  float* a0 = (float*)acts;
-  float* hidden = a0 + px * 8 * G0;                                   // layer l's output (l < nb - 1) at hidden + l px 8 Gc
-  float* last = hidden + (size_t)(nb - 1) * px * 8 * Gc;
-  DPX_LAUNCH("k_bx_pack_in", k_bx_pack_in, dim3(grid_for((long)(px * 8 * G0), 256, 8192)), dim3(256), 0, s, x, sigma, a0, B, in_nc, H, W, H2, W2, G0, 0);
-  const char* wl = (const char*)packed;
-  const float* cur = a0;
-  int gin = G0;
-  for (int l = 0; l < nb; ++l) {
-    const int cin = bx_cin(l, in_nc, nc), cout = bx_cout(l, in_nc, nc, nb);
-    const bool lastl = l == nb - 1;
-    float* dst = lastl ? last : hidden + (size_t)l * px * 8 * Gc;
-    const int gout = lastl ? GL : Gc;
-    if (mode == 3) launch_bx_mt<3>((cout + 31) / 32, !lastl, cur, dst, wl, gin, gout, B, H2, W2, s);
-    else launch_bx_mt<6>((cout + 31) / 32, !lastl, cur, dst, wl, gin, gout, B, H2, W2, s);
-    wl += bx_layer_bytes(cin, cout, bx_planes(mode));
-    cur = dst;
-    gin = gout;
-  }
-  DPX_LAUNCH("k_bx_unpack_out", k_bx_unpack_out, dim3(grid_for((long)B * in_nc * H * W, 256, 8192)), dim3(256), 0, s, last, y, B, in_nc, H, W, H2,
-             W2, GL);
-  return launch_status("dpx_ffdnet_forward_bf16_save");
+  return ffdnet_forward_bf16_impl("dpx_ffdnet_forward_bf16_save", true, x, y, sigma, packed, in_nc, nc, nb, mode, B, H, W, acts, stream, nullptr);
 }
 
 extern "C" size_t dpx_ffdnet_bf16_packed_transposed_bytes(int in_nc, int nc, int nb) {
@@ -1125,7 +1099,7 @@ extern "C" int dpx_admm_cg_pnp_iter(float* x, float* rhs, const float* ktb, cons
       Q.v[t] = t < nterms ? terms[t].v : nullptr;
       Q.u[t] = t < nterms ? terms[t].u : nullptr;
     }
-    rc = ffdnet_forward_bf16_impl(d, v_new, sigma, packed, in_nc, nc, nb, mode, B, H, W, ffd_ws, stream, &Q, fold_head);
+    rc = ffdnet_forward_bf16_impl("dpx_ffdnet_forward_bf16", false, d, v_new, sigma, packed, in_nc, nc, nb, mode, B, H, W, ffd_ws, stream, &Q, fold_head);
     return rc ? rc : n_cg;
   }
   DPX_REQUIRE(!rho_next, "dpx_admm_cg_pnp_iter: rho_next without the folded tail (see dpx_admm_cg_pnp_iter_folds)");

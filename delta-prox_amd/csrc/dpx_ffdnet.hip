@@ -420,26 +420,27 @@ extern "C" size_t dpx_ffdnet_ws_bytes(int B, int in_nc, int nc, int H, int W) {
   return (px * pad_even(4 * in_nc + 1) + 2 * px * nc + px * 4 * in_nc) * sizeof(float);
 }
 
-extern "C" int dpx_ffdnet_forward(const float* x, float* y, const float* sigma, const void* packed, int in_nc, int nc, int nb,
-                                  int B, int H, int W, void* ws, dpx_stream_t stream) {
-  DPX_REQUIRE(x && y && sigma && packed && ws, "dpx_ffdnet_forward: null pointer");
-  DPX_REQUIRE((size_t)FFD_CK * ((H + 1) / 2) * ((W + 1) / 2) < ((size_t)1 << 28), "dpx_ffdnet_forward: plane %dx%d too large for the 28-bit staging offsets", H, W);
+// The forward pass in `buf`: [packed input][hidden layers][last layer].  keep_all: every hidden layer's output stays, layer l's at slot l (the
+// training pass, dpx_ffdnet_acts_bytes); otherwise the hidden layers alternate between two slots (dpx_ffdnet_ws_bytes).  `name`: the entry point.
+static int ffdnet_forward_impl(const char* name, bool keep_all, const float* x, float* y, const float* sigma, const void* packed, int in_nc, int nc,
+                               int nb, int B, int H, int W, void* buf, dpx_stream_t stream) {
+  DPX_REQUIRE(x && y && sigma && packed && buf, "%s: null pointer", name);
+  DPX_REQUIRE((size_t)FFD_CK * ((H + 1) / 2) * ((W + 1) / 2) < ((size_t)1 << 28), "%s: plane %dx%d too large for the 28-bit staging offsets", name, H, W);
   DPX_REQUIRE(B > 0 && H > 0 && W > 0 && in_nc > 0 && nb >= 2 && nc % 2 == 0 && nc <= 96 && 4 * in_nc <= 96,
-              "dpx_ffdnet_forward: unsupported configuration (in_nc=%d nc=%d nb=%d)", in_nc, nc, nb);
+              "%s: unsupported configuration (in_nc=%d nc=%d nb=%d)", name, in_nc, nc, nb);
   hipStream_t s = (hipStream_t)stream;
   const int H2 = (H + 1) / 2, W2 = (W + 1) / 2, Cp = pad_even(4 * in_nc + 1);
   const size_t px = (size_t)B * H2 * W2;
-  float* a0 = (float*)ws;
-  float* bufA = a0 + px * Cp;
-  float* bufB = bufA + px * nc;
-  float* last = bufB + px * nc;
+  float* a0 = (float*)buf;
+  float* hidden = a0 + px * Cp;
+  float* last = hidden + (size_t)(keep_all ? nb - 1 : 2) * px * nc;
   DPX_LAUNCH("k_ffd_pack_in", k_ffd_pack_in, dim3(grid_for((long)(px * Cp), 256, 8192)), dim3(256), 0, s, x, sigma, a0, B, in_nc, H, W,
              H2, W2, Cp);
   const float* wl = (const float*)packed;
   const float* cur = a0;
   for (int l = 0; l < nb; ++l) {
     const int cin = layer_cin(l, in_nc, nc), cout = layer_cout(l, in_nc, nc, nb);
-    float* dst = (l == nb - 1) ? last : ((l & 1) ? bufB : bufA);
+    float* dst = (l == nb - 1) ? last : hidden + (size_t)(keep_all ? l : (l & 1)) * px * nc;
     const bool relu = l != nb - 1;
     switch (mtiles(cout)) {
       case 1: launch_conv<1>(relu, cur, dst, wl, pad_even(cin), cout, B, H2, W2, s); break;
@@ -451,7 +452,12 @@ extern "C" int dpx_ffdnet_forward(const float* x, float* y, const float* sigma, 
   }
   DPX_LAUNCH("k_ffd_unpack_out", k_ffd_unpack_out, dim3(grid_for((long)B * in_nc * H * W, 256, 8192)), dim3(256), 0, s, last, y, B,
              in_nc, H, W, H2, W2);
-  return launch_status("dpx_ffdnet_forward");
+  return launch_status(name);
+}
+
+extern "C" int dpx_ffdnet_forward(const float* x, float* y, const float* sigma, const void* packed, int in_nc, int nc, int nb,
+                                  int B, int H, int W, void* ws, dpx_stream_t stream) {
+  return ffdnet_forward_impl("dpx_ffdnet_forward", false, x, y, sigma, packed, in_nc, nc, nb, B, H, W, ws, stream);
 }
 
 // ---- weight gradients -------------------------------------------------------------------------------------------------
@@ -656,35 +662,7 @@ extern "C" size_t dpx_ffdnet_acts_bytes(int B, int in_nc, int nc, int nb, int H,
 
 extern "C" int dpx_ffdnet_forward_save(const float* x, float* y, const float* sigma, const void* packed, int in_nc, int nc, int nb,
                                        int B, int H, int W, void* acts, dpx_stream_t stream) {
-  DPX_REQUIRE(x && y && sigma && packed && acts, "dpx_ffdnet_forward_save: null pointer");
-  DPX_REQUIRE((size_t)FFD_CK * ((H + 1) / 2) * ((W + 1) / 2) < ((size_t)1 << 28), "dpx_ffdnet_forward_save: plane %dx%d too large for the 28-bit staging offsets", H, W);
-  DPX_REQUIRE(B > 0 && H > 0 && W > 0 && in_nc > 0 && nb >= 2 && nc % 2 == 0 && nc <= 96 && 4 * in_nc <= 96,
-              "dpx_ffdnet_forward_save: unsupported configuration (in_nc=%d nc=%d nb=%d)", in_nc, nc, nb);
-  hipStream_t s = (hipStream_t)stream;
-  const int H2 = (H + 1) / 2, W2 = (W + 1) / 2, Cp = pad_even(4 * in_nc + 1);
-  const size_t px = (size_t)B * H2 * W2;
-  float* a0 = (float*)acts;
-  float* hidden = a0 + px * Cp;                          // nb-1 buffers of px*nc
-  float* last = hidden + (size_t)(nb - 1) * px * nc;
-  DPX_LAUNCH("k_ffd_pack_in", k_ffd_pack_in, dim3(grid_for((long)(px * Cp), 256, 8192)), dim3(256), 0, s, x, sigma, a0, B, in_nc, H, W,
-             H2, W2, Cp);
-  const float* wl = (const float*)packed;
-  const float* cur = a0;
-  for (int l = 0; l < nb; ++l) {
-    const int cin = layer_cin(l, in_nc, nc), cout = layer_cout(l, in_nc, nc, nb);
-    float* dst = (l == nb - 1) ? last : hidden + (size_t)l * px * nc;
-    const bool relu = l != nb - 1;
-    switch (mtiles(cout)) {
-      case 1: launch_conv<1>(relu, cur, dst, wl, pad_even(cin), cout, B, H2, W2, s); break;
-      case 2: launch_conv<2>(relu, cur, dst, wl, pad_even(cin), cout, B, H2, W2, s); break;
-      default: launch_conv<3>(relu, cur, dst, wl, pad_even(cin), cout, B, H2, W2, s); break;
-    }
-    wl += layer_floats(cin, cout);
-    cur = dst;
-  }
-  DPX_LAUNCH("k_ffd_unpack_out", k_ffd_unpack_out, dim3(grid_for((long)B * in_nc * H * W, 256, 8192)), dim3(256), 0, s, last, y, B,
-             in_nc, H, W, H2, W2);
-  return launch_status("dpx_ffdnet_forward_save");
+  return ffdnet_forward_impl("dpx_ffdnet_forward_save", true, x, y, sigma, packed, in_nc, nc, nb, B, H, W, acts, stream);
 }
 
 // transposed layer l: input channels = forward cout (padded even), output channels = forward cin

@@ -415,41 +415,68 @@ UNROLL_BWD_MODES = (("default", {}),                                            
                     ("image-domain fused stage, reductions by its last workgroup", dict(unroll_bwd_staged=2, unroll_bwd_fold_finish=1)))
 
 
+def _unrolled_bwd_run(device, data, terms, dtype, K, knobs, chain_history=None):
+    """[loss, d loss / d rhos, d / d lams..., d / d b, d / d x0] (float64 numpy) of K unrolled ADMM iterations under the tuning `knobs`.
+    chain_history ("f32" / "bf16"): on the stage-by-stage autograd path instead (DPX_UNROLL_CHAIN, read by autodiff.run at call time: one
+    autograd node per stage), whose nodes save exactly what the one-node loop keeps as its history -- rhs (_Rhs), x (_Solve), v_i
+    (_ZUpdate); "bf16" rounds those saved images to bf16 (round-to-nearest-even, as k_hist_pack_bf16 and the emitting row kernel do)
+    through autograd's saved-tensor hooks, which makes that path keep the bf16 history's values.  A gradient autograd does not form
+    there (lambda of a prox that ignores it) counts as zeros."""
+    import contextlib
+    import os
+    from dprox import _backend as be
+    gt, b, psf = data
+    x = dp.Variable()
+    bt = T(b, device).clone().requires_grad_(True)
+    regs = []
+    if "tv" in terms:
+        regs += [dp.norm1(dp.grad(x, dim=0)), dp.norm1(dp.grad(x, dim=1))]
+    if "nn" in terms:
+        regs += [dp.nonneg(x)]
+    if "l1" in terms:
+        regs += [dp.norm1(x) * 0.5]
+    fns = dp.sum_squares(dp.conv(x, psf) - bt)
+    for r in regs:
+        fns = fns + r
+    solver = dp.specialize(dp.compile(fns, method="admm", device=device), method="unroll", device=device, max_iter=K, dtype=dtype)
+    rhos = torch.linspace(0.4, 0.2, K).requires_grad_(True)
+    lams = [torch.linspace(0.03, 0.01, K).requires_grad_(True) for _ in regs]
+    x0 = T(b, device).clone().requires_grad_(True)
+    image = lambda t: t.dtype == torch.float32 and tuple(t.shape) == tuple(b.shape)
+    hooks = contextlib.nullcontext()
+    if chain_history == "bf16":
+        hooks = torch.autograd.graph.saved_tensors_hooks(lambda t: t.bfloat16().float() if image(t) else t, lambda t: t)
+    old = os.environ.get("DPX_UNROLL_CHAIN")
+    if chain_history:
+        os.environ["DPX_UNROLL_CHAIN"] = "1"
+    try:
+        with be.tuned(**knobs):
+            with hooks:                                      # (the solver's nodes only: the loss keeps what it saves)
+                xo = solver.solve(x0=x0, rhos=rhos, lams=dict(zip(regs, lams)))
+            loss = ((xo - T(gt, device)) ** 2).mean()
+            loss.backward()
+    finally:
+        if chain_history and old is None:
+            del os.environ["DPX_UNROLL_CHAIN"]
+        elif chain_history:
+            os.environ["DPX_UNROLL_CHAIN"] = old
+    grad = lambda t: np.zeros(tuple(t.shape)) if (t.grad is None and chain_history) else t.grad.detach().cpu().double().numpy()
+    return [float(loss.detach())] + [grad(t) for t in [rhos] + lams + [bt, x0]]
+
+
 def case_unrolled_bwd_fused_vs_staged(device, shape=(2, 3, 32, 48), K=4, term_sets=("tv", "tv+nn", "nn+l1"), dtypes=("f32", "bf16"), modes=UNROLL_BWD_MODES,
                                       band=0):
     """the unrolled backward loop in its fused forms -- on power-of-two planes two kernels per backward iteration (k_bwd_rows: inverse
     row transform, rhs stage of iteration t + z stage of iteration t - 1, forward row transform; g_rhs / g_x stay in the Fourier domain),
     elsewhere the two stages as one image-domain pass (k_rhs_z_bwd4) -- against the staged loop (knob unroll_bwd_staged): same loss,
     gradients w.r.t. the rho / lambda schedules, the observation and x0 within fp32 round-off; three term sets (TV, TV + nonneg,
-    nonneg + l1 on x), fp32 and bf16 history"""
+    nonneg + l1 on x), fp32 and bf16 history.  Returns {(terms, dtype): the staged loop's [loss, gradients...]}."""
     import synthetic
-    from dprox import _backend as be
-    gt, b, psf = synthetic.deconv_case(*shape, seed=17, ksize=5, ksigma=1.2)
+    data = synthetic.deconv_case(*shape, seed=17, ksize=5, ksigma=1.2)
+    staged = {}
     for terms in term_sets:
         for dtype in dtypes:
-            res = {}
-            for name, knobs in modes:
-                x = dp.Variable()
-                bt = T(b, device).clone().requires_grad_(True)
-                regs = []
-                if "tv" in terms:
-                    regs += [dp.norm1(dp.grad(x, dim=0)), dp.norm1(dp.grad(x, dim=1))]
-                if "nn" in terms:
-                    regs += [dp.nonneg(x)]
-                if "l1" in terms:
-                    regs += [dp.norm1(x) * 0.5]
-                fns = dp.sum_squares(dp.conv(x, psf) - bt)
-                for r in regs:
-                    fns = fns + r
-                solver = dp.specialize(dp.compile(fns, method="admm", device=device), method="unroll", device=device, max_iter=K, dtype=dtype)
-                rhos = torch.linspace(0.4, 0.2, K).requires_grad_(True)
-                lams = [torch.linspace(0.03, 0.01, K).requires_grad_(True) for _ in regs]
-                x0 = T(b, device).clone().requires_grad_(True)
-                with be.tuned(unroll_bwd_band=band, **knobs):
-                    xo = solver.solve(x0=x0, rhos=rhos, lams=dict(zip(regs, lams)))
-                    loss = ((xo - T(gt, device)) ** 2).mean()
-                    loss.backward()
-                res[name] = [float(loss.detach())] + [t.grad.detach().cpu().double().numpy() for t in [rhos] + lams + [bt, x0]]
+            res = {name: _unrolled_bwd_run(device, data, terms, dtype, K, dict(unroll_bwd_band=band, **knobs)) for name, knobs in modes}
             for other in res:
                 if other == "staged":
                     continue
@@ -458,6 +485,29 @@ def case_unrolled_bwd_fused_vs_staged(device, shape=(2, 3, 32, 48), K=4, term_se
                     e = rel_l2(a, c)
                     record(f"unrolled backward, {other} vs staged, {shape[-2]} x {shape[-1]}, {terms}, {dtype}, gradient {k}", e, 1e-5)
                     assert e <= 1e-5, (terms, dtype, k, other, e)
+            staged[terms, dtype] = res["staged"]
+    return staged
+
+
+def case_unrolled_bwd_shortest_loops(device, shapes=((1, 2, 32, 48),)):
+    """the backward loops at K = 1 and K = 2, where a loop's start and end meet: at K = 1 the two-kernel loop is not selected and the
+    image-domain fused loop is its first z stage and its last rhs stage with nothing in between, at K = 2 each loop body runs once.
+    case_unrolled_bwd_fused_vs_staged (every mode against the staged loop, 1e-5), and the staged loop against the stage-by-stage
+    autograd path keeping the same history format (_unrolled_bwd_run: chain_history), 1e-5 on every gradient in both formats.
+    (Against that path with an fp32 history the bf16 history's d loss / d rho is 6e-5 ... 2e-2 away: that is the history's rounding in
+    a sum that cancels, profiles/host_loops_refactor.txt, not something a loop can get wrong.)"""
+    import synthetic
+    for shape in shapes:
+        data = synthetic.deconv_case(*shape, seed=17, ksize=5, ksigma=1.2)
+        for K in (1, 2):
+            staged = case_unrolled_bwd_fused_vs_staged(device, shape=shape, K=K, term_sets=("tv+nn",))
+            for (terms, dtype), res in staged.items():
+                chain = _unrolled_bwd_run(device, data, terms, "f32", K, {}, chain_history=dtype)
+                assert abs(res[0] - chain[0]) <= TOL * abs(chain[0]), (shape, K, dtype, res[0], chain[0])
+                for k, (a, c) in enumerate(zip(res[1:], chain[1:])):
+                    e = rel_l2(a, c)
+                    record(f"unrolled backward, staged vs stage-by-stage autograd, {'x'.join(map(str, shape))}, K = {K}, {dtype}, gradient {k}", e, 1e-5)
+                    assert e <= 1e-5, (shape, K, dtype, k, e)
 
 
 def case_unrolled_plane_sizes(device, shapes=((1, 3, 768, 1024), (1, 3, 768, 768))):

@@ -197,6 +197,31 @@ def test_unrolled_backward_two_kernel_iteration_256():
     pc.case_unrolled_bwd_fused_vs_staged(DEV, shape=(1, 1, 256, 256), K=2, term_sets=("nn+l1",), dtypes=("bf16",), modes=modes, band=5)
 
 
+def test_unrolled_backward_shortest_loops():
+    pc.case_unrolled_bwd_shortest_loops(DEV)
+
+
+def test_unrolled_forward_refuses_fresh_x0_off_the_two_kernel_iteration():
+    """both history formats: a lazy fresh state (fresh_x0) exists only for the two-kernel iteration; on a plane that is not on it the
+    entry point says so and launches nothing (it used to be the fp32 entry's rule alone)"""
+    import ctypes
+    import torch
+    from dprox import _backend as be
+    B, C, H, W, n, K = 1, 1, 12, 20, 1, 1
+    t = lambda *shape: torch.zeros(*shape)
+    planes = [t(B, C, H, W) for _ in range(6)]
+    arr = lambda ts: (ctypes.c_void_p * n)(*[x.data_ptr() for x in ts])
+    lin, prx, alp = (ctypes.c_int * n)(be.LIN_IDENTITY), (ctypes.c_int * n)(be.PROX_NONNEG), (ctypes.c_float * n)(1.0)
+    rho, lam, dummy = t(K, B), t(K, B), t(64)
+    tail = (arr(planes[0:1]), arr(planes[1:2]), lin, prx, alp, n, be.ptr(rho), arr([lam]), K, be.ptr(dummy), be.ptr(dummy), ctypes.c_float(0.0), B, C, H, W,
+            be.ptr(dummy), be.ptr(dummy), be.ptr(planes[2]), be.stream())
+    with pytest.raises(be.DpxError, match=r"dpx_admm_unrolled_forward: fresh_x0 needs the two-kernel iteration \(plane 12 x 20 is not on it\)"):
+        be.lib().call("dpx_admm_unrolled_forward", be.ptr(t(K, 2 + 2 * n, B, C, H, W)), *tail)
+    with pytest.raises(be.DpxError, match=r"dpx_admm_unrolled_forward_bf16: fresh_x0 needs the two-kernel iteration \(plane 12 x 20 is not on it\)"):
+        be.lib().call("dpx_admm_unrolled_forward_bf16", be.ptr(t(K, 2 + n, B, C, H, W)), be.ptr(t(2 + 4 * n, B, C, H, W)), be.ptr(planes[3]), arr(planes[4:5]),
+                      arr(planes[5:6]), *tail)
+
+
 def test_unrolled_gradients():
     pc.case_unrolled_grads(DEV)
 

@@ -256,6 +256,10 @@ def test_unrolled_backward_two_kernel_iteration(shape):
     pc.case_unrolled_bwd_fused_vs_staged(DEV, shape=shape, K=3, term_sets=("tv",), dtypes=("f32",), band=7)
 
 
+def test_unrolled_backward_shortest_loops():
+    pc.case_unrolled_bwd_shortest_loops(DEV, shapes=((1, 2, 32, 48), (1, 1, 256, 256)))
+
+
 def test_unrolled_gradients():
     pc.case_unrolled_grads(DEV)
 
