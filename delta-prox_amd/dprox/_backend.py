@@ -225,6 +225,14 @@ SIGNATURES = {
     "dpx_anderson_ws_bytes": (c_size_t, [c_int, c_int, c_long]),
     "dpx_anderson_gram_row": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_long, c_void_p, c_void_p]),
     "dpx_anderson_mix": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_float, c_int, c_int, c_long, c_void_p]),
+    "dpx_minres_state_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "dpx_minres_ws_bytes": (c_size_t, [c_int, c_long, c_int]),
+    "dpx_minres_init": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
+    "dpx_minres_colscale": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_long, c_int, c_int, c_void_p]),
+    "dpx_minres_alpha": (c_int, [c_void_p, c_void_p, c_void_p, c_double, c_void_p, c_int, c_int, c_long, c_int, c_int, c_void_p, c_void_p]),
+    "dpx_minres_lanczos": (c_int, [c_void_p, c_void_p, c_double, c_double, c_int, c_void_p, c_int, c_int, c_long, c_int, c_int, c_void_p, c_void_p]),
+    "dpx_minres_beta": (c_int, [c_void_p, c_void_p, c_double, c_void_p, c_int, c_int, c_long, c_int, c_int, c_void_p, c_void_p]),
+    "dpx_minres_update": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_long, c_int, c_int, c_void_p, c_void_p]),
 }
 
 

@@ -504,6 +504,85 @@ class CgControl:
         L.call("dpx_cg_update", ptr(x), ptr(r), ptr(p), ptr(Ap), ptr(self.state), self.B, self.npb, be.stream())
 
 
+class MinresControl:
+    """device-resident state of one minres() solve (dpx_minres_*): vectors are [G, N, K] (G leading systems, K contiguous columns,
+    every dot product per (g, k)), float32 or float64.  ``zring`` [2, G, N, K] is the ring of Lanczos vectors, ``search``
+    [2, S, G, N, K] the ring of search vectors, ``solution`` [S, G, N, K]; the scalars of every (shift, system) pair and the step
+    counter live in ``state`` (float64), and which slot of a ring is "prev" or "curr" follows from that counter on the device --
+    the host only issues launches.  ``fields()`` names the state's parts."""
+
+    def __init__(self, b, shifts, value=None, eps=1e-25):
+        if b.ndim != 3 or b.numel() == 0:
+            raise be.DpxError(f"minres: right-hand side of shape {tuple(b.shape)} (expected a non-empty [G, N, K])")
+        self.f64 = b.dtype == torch.float64
+        require(b, dtype=b.dtype if self.f64 else torch.float32, what="minres right-hand side")
+        self.G, self.N, self.K = (int(s) for s in b.shape)
+        shifts = shifts.detach().reshape(-1).to(device=b.device, dtype=torch.float64)
+        self.S = int(shifts.numel())
+        if self.S < 1:
+            raise be.DpxError("minres: empty shifts")
+        self.value = 1.0 if value is None else float(value)
+        self.eps = float(eps)
+        L = be.lib()
+        self.state = torch.zeros(L.query("dpx_minres_state_bytes", self.S, self.G, self.K) // 8, dtype=torch.float64, device=b.device)
+        # (the reductions' tickets live at the head of the workspace and must start from zero: not the shared scratch of workspace())
+        self.ws = torch.zeros(max(L.query("dpx_minres_ws_bytes", self.G, self.N, self.K), 16), dtype=torch.uint8, device=b.device)
+        self.fields()["shifts"].copy_(shifts)
+        kw = dict(dtype=b.dtype, device=b.device)
+        self.zring = torch.zeros((2,) + tuple(b.shape), **kw)
+        self.search = torch.zeros((2, self.S) + tuple(b.shape), **kw)
+        self.solution = torch.zeros((self.S,) + tuple(b.shape), **kw)
+        self._dims = (self.S, self.G, self.N, self.K, 1 if self.f64 else 0)
+
+    def fields(self):
+        """views into the state block: alpha [G, K], beta [2, G, K], norm, zero [G, K], cos, sin [3, S, G, K], subsub, sub, diag
+        [S, G, K], scale [2, S, G, K], shifts [S], step (int64 [1])"""
+        S, G, K = self.S, self.G, self.K
+        out, off = {}, 0
+        for name, shape in (("alpha", (G, K)), ("beta", (2, G, K)), ("norm", (G, K)), ("zero", (G, K)), ("cos", (3, S, G, K)),
+                            ("sin", (3, S, G, K)), ("subsub", (S, G, K)), ("sub", (S, G, K)), ("diag", (S, G, K)),
+                            ("scale", (2, S, G, K)), ("shifts", (S,)), ("step", (1,))):
+            n = int(np.prod(shape))
+            out[name] = self.state[off:off + n].view(shape)
+            off += n
+        out["step"] = out["step"].view(torch.int64)
+        return out
+
+    def _vec(self, t, what, shape=None):
+        require(t, dtype=torch.float64 if self.f64 else torch.float32, what=what)
+        if tuple(t.shape) != (shape or (self.G, self.N, self.K)):
+            raise be.DpxError(f"minres: {what} of shape {tuple(t.shape)} for systems of shape {(self.G, self.N, self.K)}")
+        return t
+
+    def init(self, phase):
+        be.lib().call("dpx_minres_init", ptr(self.state), int(phase), self.S, self.G, self.K, be.stream())
+
+    def colscale(self, out, inp, mode):
+        """per system: mode 0 out = inp / norm, 1 out = inp / beta[0], 2 out = 0 where the right-hand side vanished, else inp * norm"""
+        be.lib().call("dpx_minres_colscale", ptr(self._vec(out, "output")), ptr(self._vec(inp, "input")), ptr(self.state), int(mode),
+                      *self._dims, be.stream())
+
+    def alpha(self, prod, q=None, value=None):
+        """alpha = value <prod, q> per system; ``q=None``: the ring's previous vector (the identity preconditioner's q)"""
+        q = None if q is None else self._vec(q, "q")
+        be.lib().call("dpx_minres_alpha", ptr(self._vec(prod, "operator product")), ptr(q), ptr(self.zring),
+                      c_double(self.value if value is None else value), ptr(self.state), *self._dims, ptr(self.ws), be.stream())
+
+    def lanczos(self, prod, finish=True):
+        be.lib().call("dpx_minres_lanczos", ptr(self._vec(prod, "operator product")), ptr(self.zring), c_double(self.value), c_double(self.eps),
+                      1 if finish else 0, ptr(self.state), *self._dims, ptr(self.ws), be.stream())
+
+    def beta(self, qc):
+        be.lib().call("dpx_minres_beta", ptr(self.zring), ptr(self._vec(qc, "preconditioned vector")), c_double(self.eps), ptr(self.state),
+                      *self._dims, ptr(self.ws), be.stream())
+
+    def update(self, q=None, qc=None):
+        q = None if q is None else self._vec(q, "q")
+        qc = None if qc is None else self._vec(qc, "preconditioned vector")
+        be.lib().call("dpx_minres_update", ptr(self.zring), ptr(q), ptr(qc), ptr(self.search), ptr(self.solution), ptr(self.state), *self._dims,
+                      ptr(self.ws), be.stream())
+
+
 def prox(kind, v, lam, alpha=1.0, off=None, out=None):
     require(v, what="prox input")
     B = int(v.shape[0])

@@ -726,6 +726,40 @@ int dpx_anderson_gram_row(const float* X, const float* F, float* G, float* Hm, f
 int dpx_anderson_mix(const float* F, const float* G, const float* Hm, float* Xout, float* alpha, int n, int m, float beta, float lam,
                      int P, int B, long D, dpx_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------ */
+/* MINRES                                                                                      */
+/* ------------------------------------------------------------------------------------------ */
+/* minres -- linalg/solve/solver_minres.py:21-290.  Vectors are [G][N][K] (G leading systems, N unknowns, K contiguous columns;
+ * every dot product is per (g, k)), float32 or float64 (is_f64); with S shifts `search` is [2][S][G][N][K] and `solution`
+ * [S][G][N][K], both zero at the start; `zring` is the ring of two Lanczos vectors [2][G][N][K] (slot 1 holds the scaled right-hand
+ * side at the start, slot 0 zeros).  `state` (dpx_minres_state_bytes, float64 for both element types) holds per system alpha,
+ * beta[2], the right-hand side's norm and its "is zero" mark, per (shift, system) cos[3], sin[3], subsub, sub, diag, scale[2],
+ * then the S shifts (written by the caller before the first step) and the step counter; which slot is "prev" and which "curr"
+ * follows from the counter.  `ws` (dpx_minres_ws_bytes) must be zero-filled at its first use; every call leaves its head zero again.
+ * Reductions add per-workgroup partial sums in a fixed order in float64: no floating-point atomics, two calls give the same bits.
+ * 16-byte accesses when (K == 1 and N, or else K, is a multiple of 16 / sizeof(element)) and the buffers are 16-byte aligned.
+ *   dpx_minres_alpha     alpha = value <prod, q> per system; q == NULL: the ring's previous vector (identity preconditioner)
+ *   dpx_minres_lanczos   z = value prod - alpha z_prev1 - beta_prev z_prev2 written over z_prev2; finish != 0: <z, z>,
+ *                        beta_curr = max(sqrt(.), eps) and the Givens scalars of every shift (:258-282) in the same launch
+ *   dpx_minres_beta      with a preconditioner, after qc = Minv(z): <z, qc>, beta_curr and the Givens scalars
+ *   dpx_minres_update    z /= beta_curr (and qc, if given); search_curr[s] = (q - sub s1 - subsub s2) / diag over search_prev2;
+ *                        solution[s] += search_curr[s] scale_prev; advances the step counter
+ *   dpx_minres_init      phase 0: alpha holds <b, b> -> norm (below 1e-10: 1, and the mark); phase 1: alpha holds <z, q> of the
+ *                        scaled right-hand side -> beta_prev = scale_prev = sqrt(.), rotations = identity, counter = 0
+ *   dpx_minres_colscale  mode 0: out = in / norm; 1: out = in / beta[0]; 2: out = marked ? 0 : in * norm  (per system)          */
+size_t dpx_minres_state_bytes(int S, int G, int K);
+size_t dpx_minres_ws_bytes(int G, long N, int K);
+int dpx_minres_init(void* state, int phase, int S, int G, int K, dpx_stream_t stream);
+int dpx_minres_colscale(void* out, const void* in, void* state, int mode, int S, int G, long N, int K, int is_f64, dpx_stream_t stream);
+int dpx_minres_alpha(const void* prod, const void* q, const void* zring, double value, void* state, int S, int G, long N, int K, int is_f64,
+                     void* ws, dpx_stream_t stream);
+int dpx_minres_lanczos(const void* prod, void* zring, double value, double eps, int finish, void* state, int S, int G, long N, int K,
+                       int is_f64, void* ws, dpx_stream_t stream);
+int dpx_minres_beta(const void* zring, const void* qc, double eps, void* state, int S, int G, long N, int K, int is_f64, void* ws,
+                    dpx_stream_t stream);
+int dpx_minres_update(void* zring, const void* q, void* qc, void* search, void* solution, void* state, int S, int G, long N, int K,
+                      int is_f64, void* ws, dpx_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
