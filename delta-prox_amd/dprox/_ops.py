@@ -22,8 +22,10 @@ _tables = {}
 _workspaces = {}
 
 
-def _bytes(n, device):
-    return torch.empty(max(int(n), 16), dtype=torch.uint8, device=device)
+def _bytes(n, device, zero=False):
+    """the one allocation of every buffer whose size a ``*_bytes`` query of the C ABI reports (uint8; callers that need another
+    element type take ``.view(dtype)``) -- and the one hook tests/guarded_alloc.py substitutes"""
+    return (torch.zeros if zero else torch.empty)(max(int(n), 16), dtype=torch.uint8, device=device)
 
 
 def fft_table(H, W, device):
@@ -125,8 +127,7 @@ def make_otf(psf, C, H, W, device):
 
 
 def new_diag(C, H, W, device):
-    d = torch.zeros(max(be.lib().query("dpx_diag_bytes", C, H, W) // 4, 4), dtype=torch.float32, device=device)
-    return d
+    return _bytes(be.lib().query("dpx_diag_bytes", C, H, W), device, zero=True).view(torch.float32)
 
 
 def accumulate_diag(diag, psf, weight, C, H, W):
@@ -424,7 +425,7 @@ class AndersonHistory:
         self.nrm = torch.zeros(self.B, 2, **f32)
         self._alpha = torch.zeros(self.B * self.m, **f32)
         # (the reduction's tickets live at the head of the workspace and must start from zero: not the shared scratch of workspace())
-        self.ws = torch.zeros(max(be.lib().query("dpx_anderson_ws_bytes", self.B, self.P, self.D), 16), dtype=torch.uint8, device=device)
+        self.ws = _bytes(be.lib().query("dpx_anderson_ws_bytes", self.B, self.P, self.D), device, zero=True)
 
     def gram_row(self, ks, n, X=None):
         """after f(X) has been written into slot ``ks`` of F: G[ks] = F[ks] - X, row / column ks of Hm over the slots j < n, and
@@ -482,7 +483,7 @@ class CgControl:
         self.B = int(b.shape[0])
         self.npb = b.numel() // self.B
         self.dev = b.device
-        self.state = torch.empty(L.query("dpx_cg_state_bytes", self.B) // 4, dtype=torch.float32, device=b.device)
+        self.state = _bytes(L.query("dpx_cg_state_bytes", self.B), b.device).view(torch.float32)
         self.flags = self.state[5 * self.B:].view(torch.int32)                  # done, n_done, it, pad
         self.pAp = self.state[3 * self.B:4 * self.B]
         self.gram = torch.empty(self.B, self.B, dtype=torch.float32, device=b.device)
@@ -524,9 +525,9 @@ class MinresControl:
         self.value = 1.0 if value is None else float(value)
         self.eps = float(eps)
         L = be.lib()
-        self.state = torch.zeros(L.query("dpx_minres_state_bytes", self.S, self.G, self.K) // 8, dtype=torch.float64, device=b.device)
+        self.state = _bytes(L.query("dpx_minres_state_bytes", self.S, self.G, self.K), b.device, zero=True).view(torch.float64)
         # (the reductions' tickets live at the head of the workspace and must start from zero: not the shared scratch of workspace())
-        self.ws = torch.zeros(max(L.query("dpx_minres_ws_bytes", self.G, self.N, self.K), 16), dtype=torch.uint8, device=b.device)
+        self.ws = _bytes(L.query("dpx_minres_ws_bytes", self.G, self.N, self.K), b.device, zero=True)
         self.fields()["shifts"].copy_(shifts)
         kw = dict(dtype=b.dtype, device=b.device)
         self.zring = torch.zeros((2,) + tuple(b.shape), **kw)
@@ -951,7 +952,7 @@ def conv_pack(w, b, taps):
     require(w, what="conv weight")
     cout, cin = int(w.shape[0]), int(w.shape[1])
     L = be.lib()
-    blob = torch.empty(L.query("dpx_conv_packed_bytes", cin, cout, taps), dtype=torch.uint8, device=w.device)
+    blob = _bytes(L.query("dpx_conv_packed_bytes", cin, cout, taps), w.device)
     L.call("dpx_conv_pack", ptr(blob), ptr(w), ptr(b), cin, cout, taps, be.stream())
     return blob
 

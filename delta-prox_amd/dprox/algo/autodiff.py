@@ -250,7 +250,8 @@ class _UnrolledClosed(torch.autograd.Function):
         lp = (ctypes.c_void_p * n)(*[t.data_ptr() for t in lam_tabs])
         if plan.hist_bf16:
             L = be.lib()
-            hist = torch.empty((T, 2 + n) + shape, dtype=torch.bfloat16, device=dev)
+            nb = L.query("dpx_admm_unrolled_hist_bytes_bf16", n, T, B, C, H, W)
+            hist = ops._bytes(nb, dev)[:nb].view(torch.bfloat16).view((T, 2 + n) + shape)
             work = ops.workspace("unrolled_work", L.query("dpx_admm_unrolled_work_bytes_bf16", n, B, C, H, W), dev)
             x_out = torch.empty(shape, dtype=torch.float32, device=dev)
             v_out = [torch.empty(shape, dtype=torch.float32, device=dev) for _ in range(n)]
@@ -262,7 +263,8 @@ class _UnrolledClosed(torch.autograd.Function):
             ctx.save_for_backward(rho_tab, *lam_tabs)
             ctx.hist = hist
             return (x_out, *v_out, *u_out)
-        hist = torch.empty((T, 2 + 2 * n) + shape, dtype=torch.float32, device=dev)
+        nb = be.lib().query("dpx_admm_unrolled_hist_bytes", n, T, B, C, H, W)
+        hist = ops._bytes(nb, dev)[:nb].view(torch.float32).view((T, 2 + 2 * n) + shape)
         be.lib().call("dpx_admm_unrolled_forward", be.ptr(hist), vp, up, lin, prx, alp, n, be.ptr(rho_tab), lp, T, be.ptr(plan.FK), be.ptr(dd),
                       ctypes.c_float(plan.eps), B, C, H, W, be.ptr(table), be.ptr(sws), be.ptr(fresh_x0), be.stream())
         ctx.plan, ctx.T, ctx.n_off, ctx.shape = plan, T, len(offs), shape

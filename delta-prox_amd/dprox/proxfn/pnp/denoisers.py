@@ -167,7 +167,7 @@ class FFDNet(RefKeyed):
         key = (self._weights_version(), str(dev), mode)
         if self._packed_bf16 is None or self._packed_bf16[0] != key:
             L = be.lib()
-            blob = torch.empty(L.query("dpx_ffdnet_bf16_packed_bytes", self.in_nc, self.nc, self.nb), dtype=torch.uint8, device=dev)
+            blob = ops._bytes(L.query("dpx_ffdnet_bf16_packed_bytes", self.in_nc, self.nc, self.nb), dev)
             ws = [w.detach().float().contiguous() for w in self.weights]
             bs = [b.detach().float().contiguous() for b in self.biases]
             pw = (ctypes.c_void_p * self.nb)(*[w.data_ptr() for w in ws])
@@ -204,7 +204,7 @@ class FFDNet(RefKeyed):
         key = (self._weights_version(), str(dev))
         if getattr(self, "_packed_T", None) is None or self._packed_T[0] != key:
             L = be.lib()
-            blob = torch.empty(max(L.query("dpx_ffdnet_packed_transposed_bytes", self.in_nc, self.nc, self.nb), 16), dtype=torch.uint8, device=dev)
+            blob = ops._bytes(L.query("dpx_ffdnet_packed_transposed_bytes", self.in_nc, self.nc, self.nb), dev)
             ws = [w.detach().float().contiguous() for w in self.weights]
             pw = (ctypes.c_void_p * self.nb)(*[w.data_ptr() for w in ws])
             L.call("dpx_ffdnet_pack_transposed", be.ptr(blob), pw, self.in_nc, self.nc, self.nb, be.stream())
@@ -227,7 +227,7 @@ class FFDNet(RefKeyed):
         key = (self._weights_version(), str(dev), mode)
         if getattr(self, "_packed_T_bf16", None) is None or self._packed_T_bf16[0] != key:
             L = be.lib()
-            blob = torch.empty(L.query("dpx_ffdnet_bf16_packed_transposed_bytes", self.in_nc, self.nc, self.nb), dtype=torch.uint8, device=dev)
+            blob = ops._bytes(L.query("dpx_ffdnet_bf16_packed_transposed_bytes", self.in_nc, self.nc, self.nb), dev)
             ws = [w.detach().float().contiguous() for w in self.weights]
             pw = (ctypes.c_void_p * self.nb)(*[w.data_ptr() for w in ws])
             L.call("dpx_ffdnet_bf16_pack_transposed", be.ptr(blob), pw, self.in_nc, self.nc, self.nb, mode, be.stream())
@@ -240,7 +240,7 @@ class FFDNet(RefKeyed):
             self._packed = None                           # weights were updated in place (optimizer step)
         if self._packed is None or self._packed.device != dev:
             L = be.lib()
-            blob = torch.empty(max(L.query("dpx_ffdnet_packed_bytes", self.in_nc, self.nc, self.nb), 16), dtype=torch.uint8, device=dev)
+            blob = ops._bytes(L.query("dpx_ffdnet_packed_bytes", self.in_nc, self.nc, self.nb), dev)
             ws = [w.detach().float().contiguous() for w in self.weights]
             bs = [b.detach().float().contiguous() for b in self.biases]
             pw = (ctypes.c_void_p * self.nb)(*[w.data_ptr() for w in ws])
@@ -305,7 +305,7 @@ class _FFDNetSplitFn(torch.autograd.Function):
         mode = {"bf16x3": 6, "f16x2": 3, "f16x2w": 3}[net.compute_mode]
         if mode == 3:
             be.note_f16_launch()
-        acts = torch.empty(L.query("dpx_ffdnet_bf16_acts_bytes", B, net.in_nc, net.nc, net.nb, H, W), dtype=torch.uint8, device=x.device)
+        acts = ops._bytes(L.query("dpx_ffdnet_bf16_acts_bytes", B, net.in_nc, net.nc, net.nb, H, W), x.device)
         L.call("dpx_ffdnet_forward_bf16_save", be.ptr(x), be.ptr(y), be.ptr(sig), be.ptr(net.packed_bf16(mode)), net.in_nc, net.nc, net.nb, mode,
                B, H, W, be.ptr(acts), be.stream())
         ctx.net, ctx.shape = net, (B, C, H, W)
@@ -352,7 +352,7 @@ class _FFDNetFn(torch.autograd.Function):
         L = be.lib()
         x = x.contiguous()
         y = torch.empty_like(x)
-        acts = torch.empty(L.query("dpx_ffdnet_acts_bytes", B, net.in_nc, net.nc, net.nb, H, W), dtype=torch.uint8, device=x.device)
+        acts = ops._bytes(L.query("dpx_ffdnet_acts_bytes", B, net.in_nc, net.nc, net.nb, H, W), x.device)
         L.call("dpx_ffdnet_forward_save", be.ptr(x), be.ptr(y), be.ptr(sig), be.ptr(net.packed()), net.in_nc, net.nc, net.nb,
                B, H, W, be.ptr(acts), be.stream())
         ctx.net, ctx.shape = net, (B, C, H, W)
