@@ -16,7 +16,8 @@
 //
 // 16-byte accesses when D % 4 == 0 and the buffers are 16-byte aligned (every [image][D] segment is then aligned too); any other D
 // runs the same kernels element by element.
-#include "dpx_cg_dev.h"
+#include "dpx_dispatch.h"
+#include "dpx_reduce_dev.h"
 
 namespace dpx {
 namespace {
@@ -24,32 +25,6 @@ namespace {
 constexpr int AND_MAXN = 8;                 // history slots a call can mix
 constexpr int AND_NRED = AND_MAXN + 1;      // reduced values per image: the Gram row and |F_k|^2
 constexpr int AND_THREADS = 256;
-
-template <int V> struct AndVec;
-template <> struct AndVec<1> {
-  float v[1];
-  __device__ __forceinline__ static AndVec ld(const float* p, long i) { return {{p[i]}}; }
-  __device__ __forceinline__ void st(float* p, long i) const { p[i] = v[0]; }
-};
-template <> struct AndVec<4> {
-  float v[4];
-  __device__ __forceinline__ static AndVec ld(const float* p, long i) {
-    const float4 t = ((const float4*)p)[i];
-    return {{t.x, t.y, t.z, t.w}};
-  }
-  __device__ __forceinline__ void st(float* p, long i) const { ((float4*)p)[i] = make_float4(v[0], v[1], v[2], v[3]); }
-};
-
-__device__ __forceinline__ float and_wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-__device__ __forceinline__ double and_wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
 
 // grid (nblk, B).  partial: [B][AND_NRED][nblk]; counter: [B] tickets, zero between launches.
 template <int V>
@@ -69,8 +44,8 @@ __global__ void __launch_bounds__(AND_THREADS) k_anderson_gram_row(const float* 
     const float* fs = F + ks * slot + seg;
     float* gs = G + ks * slot + seg;
     for (long i = blockIdx.x * (long)AND_THREADS + tid; i < DV; i += (long)nblk * AND_THREADS) {
-      const AndVec<V> f = AndVec<V>::ld(fs, i), x = AndVec<V>::ld(xs, i);
-      AndVec<V> g;
+      const Vec<float, V> f = Vec<float, V>::ld(fs, i), x = Vec<float, V>::ld(xs, i);
+      Vec<float, V> g;
 #pragma unroll
       for (int e = 0; e < V; ++e) {
         g.v[e] = f.v[e] - x.v[e];
@@ -84,7 +59,7 @@ __global__ void __launch_bounds__(AND_THREADS) k_anderson_gram_row(const float* 
 #pragma unroll
           for (int e = 0; e < V; ++e) acc[j] = fmaf(g.v[e], g.v[e], acc[j]);
         } else {
-          const AndVec<V> o = AndVec<V>::ld(G + j * slot + seg, i);
+          const Vec<float, V> o = Vec<float, V>::ld(G + j * slot + seg, i);
 #pragma unroll
           for (int e = 0; e < V; ++e) acc[j] = fmaf(g.v[e], o.v[e], acc[j]);
         }
@@ -93,7 +68,7 @@ __global__ void __launch_bounds__(AND_THREADS) k_anderson_gram_row(const float* 
   }
 #pragma unroll
   for (int j = 0; j < AND_NRED; ++j) {
-    const float s = and_wave_sum(acc[j]);
+    const float s = wave_sum(acc[j]);
     if (lane == 0) red[wave][j] = s;
   }
   __syncthreads();
@@ -105,10 +80,7 @@ __global__ void __launch_bounds__(AND_THREADS) k_anderson_gram_row(const float* 
   if (!dpx_last_block(counter + b, (unsigned)nblk, &last)) return;
   for (int e = wave; e < AND_NRED; e += AND_THREADS / 64) {
     if (e >= n && e != AND_MAXN) continue;    // (uniform per wave)
-    const float* pe = partial + ((long)b * AND_NRED + e) * nblk;
-    double s = 0.0;
-    for (int i = lane; i < nblk; i += 64) s += (double)dpx_ld_agent(pe + i);
-    s = and_wave_sum(s);
+    const double s = sum_partials_f64(partial + ((long)b * AND_NRED + e) * nblk, nblk);
     if (lane == 0) {
       const float v = (float)s;
       if (e == AND_MAXN) {
@@ -174,17 +146,17 @@ __global__ void __launch_bounds__(AND_THREADS) k_anderson_mix(const float* __res
     const long seg = ((long)p * B + b) * D;
     float* xo = Xout + seg;
     for (long i = blockIdx.x * (long)AND_THREADS + tid; i < DV; i += (long)nblk * AND_THREADS) {
-      AndVec<V> sf, sx;
+      Vec<float, V> sf, sx;
 #pragma unroll
       for (int e = 0; e < V; ++e) sf.v[e] = sx.v[e] = 0.f;
 #pragma unroll
       for (int j = 0; j < AND_MAXN; ++j) {
         if (j >= n) continue;                            // (uniform)
-        const AndVec<V> f = AndVec<V>::ld(F + j * slot + seg, i);
+        const Vec<float, V> f = Vec<float, V>::ld(F + j * slot + seg, i);
 #pragma unroll
         for (int e = 0; e < V; ++e) sf.v[e] = fmaf(a[j], f.v[e], sf.v[e]);
         if constexpr (!BETA1) {
-          const AndVec<V> g = AndVec<V>::ld(G + j * slot + seg, i);
+          const Vec<float, V> g = Vec<float, V>::ld(G + j * slot + seg, i);
 #pragma unroll
           for (int e = 0; e < V; ++e) sx.v[e] = fmaf(a[j], f.v[e] - g.v[e], sx.v[e]);
         }
@@ -203,15 +175,13 @@ int and_blocks(int B, long D) {
   const long cap = B >= 256 ? 8 : 2048 / B;
   return (int)(nb > cap ? cap : (nb < 1 ? 1 : nb));
 }
-size_t and_counter_bytes(int B) { return (((size_t)B * sizeof(unsigned)) + 255) & ~(size_t)255; }
-bool and_al16(const void* p) { return (size_t)p % 16 == 0; }
 
 }  // namespace
 }  // namespace dpx
 
 extern "C" size_t dpx_anderson_ws_bytes(int B, int P, long D) {
   if (B < 1 || P < 1 || D < 1) return 0;
-  return dpx::and_counter_bytes(B) + (size_t)B * dpx::AND_NRED * dpx::and_blocks(B, D) * sizeof(float);
+  return dpx::ticket_bytes(B) + (size_t)B * dpx::AND_NRED * dpx::and_blocks(B, D) * sizeof(float);
 }
 
 extern "C" int dpx_anderson_gram_row(const float* X, const float* F, float* G, float* Hm, float* nrm, int ks, int n, int m, int P, int B, long D,
@@ -223,14 +193,13 @@ extern "C" int dpx_anderson_gram_row(const float* X, const float* F, float* G, f
   DPX_REQUIRE(P >= 1 && B >= 1 && B <= 65535 && D >= 1, "dpx_anderson_gram_row: bad shape P=%d B=%d D=%ld", P, B, D);
   const int nblk = and_blocks(B, D);
   unsigned* counter = (unsigned*)ws;
-  float* partial = (float*)((char*)ws + and_counter_bytes(B));
+  float* partial = (float*)((char*)ws + ticket_bytes(B));
   const dim3 grid(nblk, B, 1);
-  if (D % 4 == 0 && and_al16(X) && and_al16(F) && and_al16(G))
-    DPX_LAUNCH("k_anderson_gram_row", k_anderson_gram_row<4>, grid, dim3(AND_THREADS), 0, (hipStream_t)stream, X, F, G, Hm, nrm, partial, counter, ks, n, m,
+  dispatch_flag(D % 4 == 0 && aligned16({X, F, G}), [&](auto vec) {
+    constexpr int V = decltype(vec)::value ? 4 : 1;
+    DPX_LAUNCH("k_anderson_gram_row", k_anderson_gram_row<V>, grid, dim3(AND_THREADS), 0, (hipStream_t)stream, X, F, G, Hm, nrm, partial, counter, ks, n, m,
                P, D, nblk);
-  else
-    DPX_LAUNCH("k_anderson_gram_row", k_anderson_gram_row<1>, grid, dim3(AND_THREADS), 0, (hipStream_t)stream, X, F, G, Hm, nrm, partial, counter, ks, n, m,
-               P, D, nblk);
+  });
   return launch_status("dpx_anderson_gram_row");
 }
 
@@ -242,17 +211,12 @@ extern "C" int dpx_anderson_mix(const float* F, const float* G, const float* Hm,
   DPX_REQUIRE(P >= 1 && B >= 1 && B <= 65535 && D >= 1, "dpx_anderson_mix: bad shape P=%d B=%d D=%ld", P, B, D);
   const int nblk = and_blocks(B, D);
   const dim3 grid(nblk, B, 1);
-  const bool vec = D % 4 == 0 && and_al16(F) && and_al16(G) && and_al16(Xout);
-#define DPX_AND_MIX(V, B1)                                                                                                                       \
-  DPX_LAUNCH("k_anderson_mix", (k_anderson_mix<V, B1>), grid, dim3(AND_THREADS), 0, (hipStream_t)stream, F, G, Hm, Xout, alpha, n, m, beta, lam, P, D, \
-             nblk)
-  if (beta == 1.f) {
-    if (vec) DPX_AND_MIX(4, true);
-    else DPX_AND_MIX(1, true);
-  } else {
-    if (vec) DPX_AND_MIX(4, false);
-    else DPX_AND_MIX(1, false);
-  }
-#undef DPX_AND_MIX
+  dispatch_flag(beta == 1.f, [&](auto beta1) {
+    dispatch_flag(D % 4 == 0 && aligned16({F, G, Xout}), [&](auto vec) {
+      constexpr int V = decltype(vec)::value ? 4 : 1;
+      DPX_LAUNCH("k_anderson_mix", (k_anderson_mix<V, decltype(beta1)::value>), grid, dim3(AND_THREADS), 0, (hipStream_t)stream, F, G, Hm, Xout, alpha, n, m,
+                 beta, lam, P, D, nblk);
+    });
+  });
   return launch_status("dpx_anderson_mix");
 }

@@ -9,28 +9,9 @@
 //       (J and dprox/dlam are recovered from the saved OUTPUT v: soft-threshold passes where v != 0, nonneg where v > 0)
 //   x stage       g_rho = -<g_rhs, sum_i K_i^T K_i x>            (g_rhs = M g_x comes from dpx_fourier_apply_inv)
 //   rhs stage     g_v_i = rho K_i g, g_u_i = -g_v_i, g_rho = <g, rhs> / rho
-#include "dpx_cg_dev.h"
+#include "dpx_reduce_dev.h"
 
 namespace dpx {
-
-__device__ __forceinline__ float ad_wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-__device__ __forceinline__ float ad_block_sum(float v, float* sh) {
-  v = ad_wave_sum(v);
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  __syncthreads();
-  if (lane == 0) sh[wid] = v;
-  __syncthreads();
-  float r = 0.f;
-  if (wid == 0) {
-    r = lane < (int)(blockDim.x >> 6) ? sh[lane] : 0.f;
-    r = ad_wave_sum(r);
-  }
-  return r;                                              // valid in thread 0
-}
 
 struct BwdTerm {
   int linop, prox;
@@ -104,7 +85,7 @@ __global__ void __launch_bounds__(256) k_zupdate_bwd(float* __restrict__ gx, Bwd
     gx[i] = acc;
   }
   for (int t = 0; t < T.n; ++t) {
-    const float s = ad_block_sum(lsum[t], sh);
+    const float s = block_sum(lsum[t], sh);
     if (threadIdx.x == 0) part[((long)t * gridDim.y + b) * gridDim.x + blockIdx.x] = s * T.t[t].alpha;
   }
 }
@@ -178,7 +159,7 @@ __global__ void __launch_bounds__(256) k_zupdate_bwd4(float* __restrict__ gx, Bw
     *(float4*)(gx + i) = make_float4(acc[0], acc[1], acc[2], acc[3]);
   }
   for (int t = 0; t < T.n; ++t) {
-    const float s = ad_block_sum(lsum[t], sh);
+    const float s = block_sum(lsum[t], sh);
     if (threadIdx.x == 0) part[((long)t * gridDim.y + b) * gridDim.x + blockIdx.x] = s * T.t[t].alpha;
   }
 }
@@ -221,7 +202,7 @@ __global__ void __launch_bounds__(256) k_solve_rho_grad(const float* __restrict_
     }
     acc = fmaf(g[i], lx, acc);
   }
-  const float s = ad_block_sum(acc, sh);
+  const float s = block_sum(acc, sh);
   if (threadIdx.x == 0) part[(long)b * gridDim.x + blockIdx.x] = -s;
 }
 
@@ -262,7 +243,7 @@ __global__ void __launch_bounds__(256) k_rhs_bwd(const float* __restrict__ g, co
       }
     }
   }
-  const float s = ad_block_sum(acc, sh);
+  const float s = block_sum(acc, sh);
   if (threadIdx.x == 0) part[(long)b * gridDim.x + blockIdx.x] = s;
 }
 
@@ -310,9 +291,9 @@ __global__ void __launch_bounds__(256) k_solve_rhs_bwd(const float* __restrict__
       }
     }
   }
-  const float sa = ad_block_sum(acc_a, sh);
+  const float sa = block_sum(acc_a, sh);
   __syncthreads();
-  const float sb = ad_block_sum(acc_b, sh);
+  const float sb = block_sum(acc_b, sh);
   if (threadIdx.x == 0) {
     part_a[(long)b * gridDim.x + blockIdx.x] = -sa;
     part_b[(long)b * gridDim.x + blockIdx.x] = sb;
@@ -389,9 +370,9 @@ __global__ void __launch_bounds__(256) k_solve_rhs_bwd4(const float* __restrict_
       }
     }
   }
-  const float sa = ad_block_sum(acc_a, sh);
+  const float sa = block_sum(acc_a, sh);
   __syncthreads();
-  const float sb = ad_block_sum(acc_b, sh);
+  const float sb = block_sum(acc_b, sh);
   if (threadIdx.x == 0) {
     part_a[(long)b * gridDim.x + blockIdx.x] = -sa;
     part_b[(long)b * gridDim.x + blockIdx.x] = sb;
@@ -403,7 +384,7 @@ __global__ void k_ad_finish(const float* __restrict__ part, float* __restrict__ 
   __shared__ float sh[16];
   float acc = 0.f;
   for (int i = threadIdx.x; i < nblk; i += blockDim.x) acc += part[(long)blockIdx.x * nblk + i];
-  acc = ad_block_sum(acc, sh);
+  acc = block_sum(acc, sh);
   if (threadIdx.x == 0) out[blockIdx.x] = (div ? acc / div[blockIdx.x] : acc) + (add ? add[blockIdx.x] : 0.f);
 }
 
@@ -416,16 +397,16 @@ __global__ void k_ad_finish_iter(const float* __restrict__ part_lam, const float
   if (j < nB) {
     float acc = 0.f;
     for (int i = threadIdx.x; i < nblk; i += blockDim.x) acc += part_lam[(long)j * nblk + i];
-    acc = ad_block_sum(acc, sh);
+    acc = block_sum(acc, sh);
     if (threadIdx.x == 0) glam[j] = acc;
   } else {
     const int b = j - nB;
     float a = 0.f, c = 0.f;
     for (int i = threadIdx.x; i < nblk; i += blockDim.x) a += part_a[(long)b * nblk + i];
-    a = ad_block_sum(a, sh);
+    a = block_sum(a, sh);
     __syncthreads();
     for (int i = threadIdx.x; i < nblk; i += blockDim.x) c += part_b[(long)b * nblk + i];
-    c = ad_block_sum(c, sh);
+    c = block_sum(c, sh);
     if (threadIdx.x == 0) grho[b] = a + c / rho[b];
   }
 }
@@ -441,7 +422,7 @@ __global__ void k_ad_finish_all(const float* __restrict__ part, long stride, flo
   if (j < nB) {
     float acc = 0.f;
     for (int i = threadIdx.x; i < nblk; i += blockDim.x) acc += p[(long)j * nblk + i];
-    acc = ad_block_sum(acc, sh);
+    acc = block_sum(acc, sh);
     if (threadIdx.x == 0) glam[(long)(it - 1) * nB + j] = acc;
   } else {
     const int b = j - nB;
@@ -449,10 +430,10 @@ __global__ void k_ad_finish_all(const float* __restrict__ part, long stride, flo
     const float* pb = pa + (long)B * nblk;
     float a = 0.f, c = 0.f;
     for (int i = threadIdx.x; i < nblk; i += blockDim.x) a += pa[(long)b * nblk + i];
-    a = ad_block_sum(a, sh);
+    a = block_sum(a, sh);
     __syncthreads();
     for (int i = threadIdx.x; i < nblk; i += blockDim.x) c += pb[(long)b * nblk + i];
-    c = ad_block_sum(c, sh);
+    c = block_sum(c, sh);
     if (threadIdx.x == 0) grho[(long)it * B + b] = a + c / rho_tab[(long)it * B + b];
   }
 }
@@ -642,16 +623,16 @@ __global__ void __launch_bounds__(256) k_rhs_z_bwd4(const float* __restrict__ g,
     }
     *(float4*)(gx + i) = make_float4(acc[0], acc[1], acc[2], acc[3]);
   }
-  const float sa = ad_block_sum(acc_a, sh);
+  const float sa = block_sum(acc_a, sh);
   __syncthreads();
-  const float sb = ad_block_sum(acc_b, sh);
+  const float sb = block_sum(acc_b, sh);
   if (threadIdx.x == 0) {
     dpx_st_agent(part_a + (long)b * gridDim.x + blockIdx.x, -sa);
     dpx_st_agent(part_b + (long)b * gridDim.x + blockIdx.x, sb);
   }
   for (int t = 0; t < T.n; ++t) {
     __syncthreads();
-    const float s = ad_block_sum(lsum[t], sh);
+    const float s = block_sum(lsum[t], sh);
     if (threadIdx.x == 0) dpx_st_agent(part_lam + ((long)t * gridDim.y + b) * gridDim.x + blockIdx.x, s * T.t[t].alpha);
   }
   if (!counter) return;
@@ -662,16 +643,16 @@ __global__ void __launch_bounds__(256) k_rhs_z_bwd4(const float* __restrict__ g,
     if (j < nB) {
       float acc = 0.f;
       for (int i = threadIdx.x; i < nblk; i += blockDim.x) acc += dpx_ld_agent(part_lam + (long)j * nblk + i);
-      acc = ad_block_sum(acc, sh);
+      acc = block_sum(acc, sh);
       if (threadIdx.x == 0) glam[j] = acc;
     } else {
       const int bb = j - nB;
       float a = 0.f, c = 0.f;
       for (int i = threadIdx.x; i < nblk; i += blockDim.x) a += dpx_ld_agent(part_a + (long)bb * nblk + i);
-      a = ad_block_sum(a, sh);
+      a = block_sum(a, sh);
       __syncthreads();
       for (int i = threadIdx.x; i < nblk; i += blockDim.x) c += dpx_ld_agent(part_b + (long)bb * nblk + i);
-      c = ad_block_sum(c, sh);
+      c = block_sum(c, sh);
       if (threadIdx.x == 0) grho[bb] = a + c / rho[bb];
     }
   }

@@ -2,6 +2,7 @@
 // dpx_bwd_rows_par.hip: the rows of a band side by side).  Not part of the C ABI.
 #pragma once
 #include "dpx_fft_reg.h"
+#include "dpx_reduce_dev.h"
 
 namespace dpx {
 
@@ -57,12 +58,6 @@ template <int KIND, int V> __device__ __forceinline__ float bwd_gd_row(float sq,
     w[m].y = bwd_gd<KIND>(sq, rho * w[m].y, av[m].y, vv[m].y, lt);
   }
   return lt;
-}
-
-__device__ __forceinline__ float bwd_wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
 }
 
 }  // namespace dpx

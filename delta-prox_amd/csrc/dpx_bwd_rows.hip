@@ -275,10 +275,10 @@ __global__ void __launch_bounds__(256, (NT >= 3 || (NT == 2 && !HB)) ? 1 : 2) k_
   {
     const int wave = tid >> 6;
     float vals[2 + NT];
-    vals[0] = bwd_wave_sum(acc_a);
-    vals[1] = bwd_wave_sum(acc_b);
+    vals[0] = wave_sum(acc_a);
+    vals[1] = wave_sum(acc_b);
 #pragma unroll
-    for (int i = 0; i < NT; ++i) vals[2 + i] = bwd_wave_sum(lsum[i]);
+    for (int i = 0; i < NT; ++i) vals[2 + i] = wave_sum(lsum[i]);
     __syncthreads();
     if (lane == 0) {
 #pragma unroll

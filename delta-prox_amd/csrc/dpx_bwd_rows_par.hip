@@ -323,14 +323,9 @@ __global__ void __launch_bounds__(64 * NW, 4) k_bwd_rows_par(const float2* __res
   }
   // ---- the workgroup's partial sums, one slot each (the finishing launch adds the slots of an image in index order) ----
   {
-    auto wave_sum_d = [](double v) {
-#pragma unroll
-      for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-      return v;
-    };
     double vals[2 + NT];
 #pragma unroll
-    for (int i = 0; i < NT; ++i) vals[2 + i] = wave_sum_d((double)lsum[i]);
+    for (int i = 0; i < NT; ++i) vals[2 + i] = wave_sum((double)lsum[i]);
     if (lane == 0) {
       if (!wave_live) red[wave * (2 + DPX_MAX_TERMS) + 0] = red[wave * (2 + DPX_MAX_TERMS) + 1] = 0.0;     // (idle waves: their two slots were not written above)
 #pragma unroll

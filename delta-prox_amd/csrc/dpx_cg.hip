@@ -17,6 +17,7 @@
 #include <cstdlib>
 
 #include "dpx_cg_dev.h"
+#include "dpx_dispatch.h"
 
 namespace dpx {
 
@@ -46,51 +47,42 @@ __global__ void __launch_bounds__(64) k_cg_test(CgState S, const float* __restri
   cg_test_block(S, G, M, sh, -1.f);
 }
 
-// p = r + beta_b * p        (solver_cg.py:111-115; beta = 0 in the first iteration)
-__global__ void k_cg_direction(float* __restrict__ p, const float* __restrict__ r, CgState S, long npb4) {
+// p = r + beta_b * p        (solver_cg.py:111-115; beta = 0 in the first iteration).  V = 4: 16-byte accesses; npbv = n_per_batch / V
+template <int V> __global__ void k_cg_direction(float* __restrict__ p, const float* __restrict__ r, CgState S, long npbv) {
   if (S.flags()[0]) return;
   const int b = blockIdx.y;
   const float beta = S.beta()[b];
-  float4* pb = (float4*)p + (long)b * npb4;
-  const float4* rb = (const float4*)r + (long)b * npb4;
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < npb4; i += (long)gridDim.x * blockDim.x) {
-    const float4 rv = rb[i], pv = pb[i];
-    pb[i] = make_float4(fmaf(beta, pv.x, rv.x), fmaf(beta, pv.y, rv.y), fmaf(beta, pv.z, rv.z), fmaf(beta, pv.w, rv.w));
+  float* pb = p + (long)b * npbv * V;
+  const float* rb = r + (long)b * npbv * V;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < npbv; i += (long)gridDim.x * blockDim.x) {
+    const Vec<float, V> rv = Vec<float, V>::ld(rb, i);
+    Vec<float, V> pv = Vec<float, V>::ld(pb, i);
+#pragma unroll
+    for (int e = 0; e < V; ++e) pv.v[e] = fmaf(beta, pv.v[e], rv.v[e]);
+    pv.st(pb, i);
   }
-}
-__global__ void k_cg_direction1(float* __restrict__ p, const float* __restrict__ r, CgState S, long npb) {
-  if (S.flags()[0]) return;
-  const int b = blockIdx.y;
-  const float beta = S.beta()[b];
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < npb; i += (long)gridDim.x * blockDim.x)
-    p[(long)b * npb + i] = fmaf(beta, p[(long)b * npb + i], r[(long)b * npb + i]);
 }
 
 // alpha_b = gamma_b / <p_b, A p_b>;  x += alpha p;  r -= alpha A p       (solver_cg.py:122-127)
-__global__ void k_cg_update(float* __restrict__ x, float* __restrict__ r, const float* __restrict__ p, const float* __restrict__ Ap, CgState S,
-                            long npb4) {
+template <int V>
+__global__ void k_cg_update(float* __restrict__ x, float* __restrict__ r, const float* __restrict__ p, const float* __restrict__ Ap, CgState S, long npbv) {
   if (S.flags()[0]) return;
   const int b = blockIdx.y;
   const float alpha = S.gamma()[b] / S.pAp()[b];
-  float4* xb = (float4*)x + (long)b * npb4;
-  float4* rb = (float4*)r + (long)b * npb4;
-  const float4* pb = (const float4*)p + (long)b * npb4;
-  const float4* qb = (const float4*)Ap + (long)b * npb4;
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < npb4; i += (long)gridDim.x * blockDim.x) {
-    const float4 pv = pb[i], qv = qb[i], xv = xb[i], rv = rb[i];
-    xb[i] = make_float4(fmaf(alpha, pv.x, xv.x), fmaf(alpha, pv.y, xv.y), fmaf(alpha, pv.z, xv.z), fmaf(alpha, pv.w, xv.w));
-    rb[i] = make_float4(fmaf(-alpha, qv.x, rv.x), fmaf(-alpha, qv.y, rv.y), fmaf(-alpha, qv.z, rv.z), fmaf(-alpha, qv.w, rv.w));
-  }
-}
-__global__ void k_cg_update1(float* __restrict__ x, float* __restrict__ r, const float* __restrict__ p, const float* __restrict__ Ap, CgState S,
-                             long npb) {
-  if (S.flags()[0]) return;
-  const int b = blockIdx.y;
-  const float alpha = S.gamma()[b] / S.pAp()[b];
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < npb; i += (long)gridDim.x * blockDim.x) {
-    const long e = (long)b * npb + i;
-    x[e] = fmaf(alpha, p[e], x[e]);
-    r[e] = fmaf(-alpha, Ap[e], r[e]);
+  float* xb = x + (long)b * npbv * V;
+  float* rb = r + (long)b * npbv * V;
+  const float* pb = p + (long)b * npbv * V;
+  const float* qb = Ap + (long)b * npbv * V;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < npbv; i += (long)gridDim.x * blockDim.x) {
+    const Vec<float, V> pv = Vec<float, V>::ld(pb, i), qv = Vec<float, V>::ld(qb, i);
+    Vec<float, V> xv = Vec<float, V>::ld(xb, i), rv = Vec<float, V>::ld(rb, i);
+#pragma unroll
+    for (int e = 0; e < V; ++e) {
+      xv.v[e] = fmaf(alpha, pv.v[e], xv.v[e]);
+      rv.v[e] = fmaf(-alpha, qv.v[e], rv.v[e]);
+    }
+    xv.st(xb, i);
+    rv.st(rb, i);
   }
 }
 
@@ -138,23 +130,22 @@ extern "C" int dpx_cg_test(void* state, const float* gram, int B, dpx_stream_t s
 extern "C" int dpx_cg_direction(float* p, const float* r, void* state, int B, long n_per_batch, dpx_stream_t stream) {
   DPX_REQUIRE(p && r && state && B >= 1 && n_per_batch > 0, "dpx_cg_direction: bad arguments");
   const CgState S{(float*)state, B};
-  if (n_per_batch % 4 == 0 && ((size_t)p % 16 == 0) && ((size_t)r % 16 == 0))
-    DPX_LAUNCH("k_cg_direction", k_cg_direction, dim3(grid_for(n_per_batch / 4, 256, 1024), B), dim3(256), 0, (hipStream_t)stream, p, r, S,
-               n_per_batch / 4);
-  else
-    DPX_LAUNCH("k_cg_direction", k_cg_direction1, dim3(grid_for(n_per_batch, 256, 1024), B), dim3(256), 0, (hipStream_t)stream, p, r, S, n_per_batch);
+  dispatch_flag(n_per_batch % 4 == 0 && aligned16({p, r}), [&](auto vec) {
+    constexpr int V = decltype(vec)::value ? 4 : 1;
+    DPX_LAUNCH("k_cg_direction", k_cg_direction<V>, dim3(grid_for(n_per_batch / V, 256, 1024), B), dim3(256), 0, (hipStream_t)stream, p, r, S,
+               n_per_batch / V);
+  });
   return launch_status("dpx_cg_direction");
 }
 
 extern "C" int dpx_cg_update(float* x, float* r, const float* p, const float* Ap, void* state, int B, long n_per_batch, dpx_stream_t stream) {
   DPX_REQUIRE(x && r && p && Ap && state && B >= 1 && n_per_batch > 0, "dpx_cg_update: bad arguments");
   const CgState S{(float*)state, B};
-  const bool al = ((size_t)x % 16 == 0) && ((size_t)r % 16 == 0) && ((size_t)p % 16 == 0) && ((size_t)Ap % 16 == 0);
-  if (n_per_batch % 4 == 0 && al)
-    DPX_LAUNCH("k_cg_update", k_cg_update, dim3(grid_for(n_per_batch / 4, 256, 1024), B), dim3(256), 0, (hipStream_t)stream, x, r, p, Ap, S,
-               n_per_batch / 4);
-  else
-    DPX_LAUNCH("k_cg_update", k_cg_update1, dim3(grid_for(n_per_batch, 256, 1024), B), dim3(256), 0, (hipStream_t)stream, x, r, p, Ap, S, n_per_batch);
+  dispatch_flag(n_per_batch % 4 == 0 && aligned16({x, r, p, Ap}), [&](auto vec) {
+    constexpr int V = decltype(vec)::value ? 4 : 1;
+    DPX_LAUNCH("k_cg_update", k_cg_update<V>, dim3(grid_for(n_per_batch / V, 256, 1024), B), dim3(256), 0, (hipStream_t)stream, x, r, p, Ap, S,
+               n_per_batch / V);
+  });
   return launch_status("dpx_cg_update");
 }
 

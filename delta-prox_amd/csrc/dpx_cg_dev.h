@@ -1,8 +1,8 @@
 // Device-side pieces of the conjugate-gradient control shared by the kernels that carry it in their epilogues (dpx_cg.hip,
-// dpx_elementwise.hip, dpx_fft.hip): the state block, the stop rule, and the "last workgroup to arrive finishes the reduction"
-// hand-over (no spinning: a workgroup never waits for another one).
+// dpx_elementwise.hip, dpx_fft.hip): the state block and the stop rule.  The "last workgroup to arrive finishes the reduction"
+// hand-over those epilogues run behind is in dpx_reduce_dev.h.
 #pragma once
-#include "dpx_common.h"
+#include "dpx_reduce_dev.h"
 
 namespace dpx {
 
@@ -17,54 +17,6 @@ struct CgState {
   __host__ __device__ float* tol2() const { return f + 4 * B; }
   __host__ __device__ int* flags() const { return (int*)(f + 5 * B); }     // done, n_done, it
 };
-
-// a value another workgroup (possibly behind another XCD's L2) wrote before it took its ticket.  dpx_last_block's acquire fence
-// (agent scope: the L2's non-coherent lines are invalidated) makes plain loads safe; atomic (sc1) loads here serialised into one
-// memory round trip each -- 13 .. 200 dependent round trips per wave: the fused iteration ran 20 % SLOWER than the unfused one.
-__device__ __forceinline__ float dpx_ld_agent(const float* p) { return *p; }
-
-// Every workgroup calls this after its own results are written: release them (agent scope), take a ticket, and learn -- uniformly --
-// whether it is the last of `nblocks` to arrive; the last one acquires and resets the counter for the next launch.
-//
-// The results a workgroup hands over must have been written with dpx_st_agent (write-through stores): the release side is then just
-// "my stores have completed" (s_waitcnt) in front of an agent-scope ticket -- a full release fence writes the XCD's whole L2 back,
-// once per workgroup: measured 47 us on an 800-workgroup launch whose own work takes 9 us.  Only the last workgroup pays an acquire
-// (L2 invalidate) before it reads the others' results with plain loads.
-#ifndef DPX_LAST_BLOCK_FULL_FENCE
-#define DPX_LAST_BLOCK_FULL_FENCE 0
-#endif
-__device__ __forceinline__ void dpx_st_agent(float* p, float v) {
-#ifdef DPX_EMULATED
-  *p = v;
-#else
-  __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#endif
-}
-__device__ __forceinline__ bool dpx_last_block(unsigned* counter, unsigned nblocks, int* sh_flag) {
-#ifdef DPX_EMULATED
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    const unsigned ticket = atomicAdd(counter, 1u);
-    *sh_flag = (ticket == nblocks - 1);
-    if (ticket == nblocks - 1) *counter = 0u;
-  }
-  __syncthreads();
-  return *sh_flag != 0;
-#else
-  if (DPX_LAST_BLOCK_FULL_FENCE) __threadfence();
-  else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    const unsigned ticket = __hip_atomic_fetch_add(counter, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    *sh_flag = (ticket == nblocks - 1);
-    if (ticket == nblocks - 1) __hip_atomic_store(counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
-  __syncthreads();
-  const bool last = *sh_flag != 0;
-  if (last) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-  return last;
-#endif
-}
 
 // The stop rule of cg() (solver_cg.py:103-104) and, if the solve goes on, beta / gamma of the next iteration (:109-115), from the
 // B x B Gram matrix G of the residuals.  M: 64 * 65 doubles and sh: 2 ints of shared memory; every thread of the workgroup calls it

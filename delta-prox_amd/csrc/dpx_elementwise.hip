@@ -338,22 +338,6 @@ __global__ void k_lincomb(float* __restrict__ out, LinPack L, int B, long npb) {
 // batched dot products: per-block partials (wave shuffles + one LDS hop), then a tiny finishing pass.
 // Deterministic (no atomics): the CG iterates must be reproducible run to run.
 // ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-__device__ __forceinline__ float block_sum(float v, float* sh) {
-  v = wave_sum(v);
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  if (lane == 0) sh[wid] = v;
-  __syncthreads();
-  const int nw = (blockDim.x + 63) >> 6;
-  float r = (threadIdx.x < nw) ? sh[threadIdx.x] : 0.f;
-  if (wid == 0) r = wave_sum(r);
-  return r;   // valid in wave 0
-}
-
 // grid (nblk, B, Bj): partial[(bi*Bj + bj)*nblk + blk] = sum over a slice of <x[bi], y[bj or bi]>
 __global__ void k_dot_partial(const float* __restrict__ x, const float* __restrict__ y, float* __restrict__ partial,
                               long npb, int gram) {
@@ -679,8 +663,6 @@ static int dot_blocks(long npb) {
   return (int)g;
 }
 
-static bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
 static int pack_terms(TermPack& T, const dpx_term* terms, int n, const char* who, bool& vec_ok) {
   if (n < 0 || n > DPX_MAX_TERMS || (n > 0 && !terms)) {
     set_error("%s: nterms must be in [0, %d]", who, DPX_MAX_TERMS);
@@ -697,7 +679,7 @@ static int pack_terms(TermPack& T, const dpx_term* terms, int n, const char* who
       set_error("%s: term %d has an unknown linop/prox code", who, i);
       return DPX_ERR_ARG;
     }
-    vec_ok &= aligned16(terms[i].v) && aligned16(terms[i].u) && aligned16(terms[i].u_out);
+    vec_ok &= aligned16({terms[i].v, terms[i].u, terms[i].u_out});
   }
   return DPX_OK;
 }
@@ -710,7 +692,7 @@ extern "C" int dpx_admm_zupdate(const float* x, const dpx_term* terms, int nterm
                                 dpx_stream_t stream) {
   DPX_REQUIRE(x && B > 0 && C > 0 && H > 0 && W > 0, "dpx_admm_zupdate: bad arguments");
   TermPack T;
-  bool vec = (W % 4 == 0) && aligned16(x);
+  bool vec = (W % 4 == 0) && aligned16({x});
   int rc = pack_terms(T, terms, nterms, "dpx_admm_zupdate", vec);
   if (rc) return rc;
   if (nterms == 0) return DPX_OK;
@@ -726,7 +708,7 @@ extern "C" int dpx_admm_rhs(float* rhs, const float* ktb, const float* rho, cons
                             int H, int W, dpx_stream_t stream) {
   DPX_REQUIRE(rhs && rho && B > 0 && C > 0 && H > 0 && W > 0, "dpx_admm_rhs: bad arguments");
   TermPack T;
-  bool vec = (W % 4 == 0) && aligned16(rhs) && (!ktb || aligned16(ktb));
+  bool vec = (W % 4 == 0) && aligned16({rhs, ktb});
   int rc = pack_terms(T, terms, nterms, "dpx_admm_rhs", vec);
   if (rc) return rc;
   const long n = (long)B * C * H * W;
@@ -784,7 +766,7 @@ extern "C" int dpx_admm_zupdate_rhs(const float* x, const dpx_term* terms, int n
                                     int dual, int emit_v, int B, int C, int H, int W, dpx_stream_t stream) {
   DPX_REQUIRE(x && rhs && rho_next && rhs != x && B > 0 && C > 0 && H > 0 && W > 0 && nterms > 0, "dpx_admm_zupdate_rhs: bad arguments");
   TermPack T;
-  bool vec = (W % 4 == 0) && aligned16(x) && aligned16(rhs) && (!ktb || aligned16(ktb));
+  bool vec = (W % 4 == 0) && aligned16({x, rhs, ktb});
   int rc = pack_terms(T, terms, nterms, "dpx_admm_zupdate_rhs", vec);
   if (rc) return rc;
   for (int i = 0; i < nterms; ++i)
@@ -1131,8 +1113,8 @@ int gram_test_fused(float* r, float* G, void* state, int B, long n_per_batch, vo
     cap = cap < 32 ? 32 : cap;
     if (nblk > cap) nblk = cap;
   }
-  const bool al16 = ((size_t)r % 16 == 0) && (!x || (((size_t)x % 16 == 0) && ((size_t)p % 16 == 0) && ((size_t)Ap % 16 == 0)));
-  if (B <= 8 && n_per_batch % 4 == 0 && al16 && tune(TUNE_CG_GRAM_SMALL) != 2) {
+  const bool vec = x ? aligned16({r, x, p, Ap}) : aligned16({r});       // (p and Ap are only touched by the update)
+  if (B <= 8 && n_per_batch % 4 == 0 && vec && tune(TUNE_CG_GRAM_SMALL) != 2) {
     int nb = (int)((n_per_batch / 4 + 255) / 256);
     nb = nb > 256 ? 256 : (nb < 1 ? 1 : nb);
     const CgState S{(float*)state, B};

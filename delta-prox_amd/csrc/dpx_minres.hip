@@ -25,9 +25,8 @@
 // A thread keeps the same columns for the whole launch (its stride over the flat index is a multiple of the row length), so the
 // per-column scalars are registers.  16-byte accesses when K == 1 and N is a multiple of the vector length, or else K is, and the
 // buffers are 16-byte aligned; element by element otherwise (no peeled head or tail).
-#include <initializer_list>
-
-#include "dpx_cg_dev.h"
+#include "dpx_dispatch.h"
+#include "dpx_reduce_dev.h"
 
 namespace dpx {
 namespace {
@@ -56,42 +55,6 @@ struct MrState {
   __host__ __device__ long long* step() const { return (long long*)(shifts() + S); }
   __host__ __device__ static size_t doubles(long S, long G, long K) { return (size_t)(5 * G * K + 11 * S * G * K + S + 1); }
 };
-
-template <class T, int V> struct MrVec {
-  T v[V];
-  __device__ __forceinline__ static MrVec ld(const T* p, long i) {
-    MrVec r;
-    if constexpr (V == 1) {
-      r.v[0] = p[i];
-    } else if constexpr (sizeof(T) == 4) {
-      const float4 t = ((const float4*)p)[i];
-      r.v[0] = t.x, r.v[1] = t.y, r.v[2] = t.z, r.v[3] = t.w;
-    } else {
-      const double2 t = ((const double2*)p)[i];
-      r.v[0] = t.x, r.v[1] = t.y;
-    }
-    return r;
-  }
-  __device__ __forceinline__ void st(T* p, long i) const {
-    if constexpr (V == 1) p[i] = v[0];
-    else if constexpr (sizeof(T) == 4) ((float4*)p)[i] = make_float4(v[0], v[1], v[2], v[3]);
-    else ((double2*)p)[i] = make_double2(v[0], v[1]);
-  }
-};
-
-template <class T> __device__ __forceinline__ T mr_wave_sum(T v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-__device__ __forceinline__ void mr_st_agent(float* p, float v) { dpx_st_agent(p, v); }
-__device__ __forceinline__ void mr_st_agent(double* p, double v) {
-#ifdef DPX_EMULATED
-  *p = v;
-#else
-  __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#endif
-}
 
 // Which flat vector indices of a leading system a thread visits: i = t, t + stride, ... with stride the largest multiple of the
 // row length (in vectors) that the launch's threads cover, so that i % KV -- the thread's column group -- never changes.
@@ -159,7 +122,7 @@ __global__ void __launch_bounds__(MR_THREADS) k_minres_pass(const T* __restrict_
         const T* xs = (x ? x : zring + cur * GNK) + seg;
         const T* ys = (y ? y : zring + (1 - cur) * GNK) + seg;
         for (long i = w.first; i < w.count; i += w.stride) {
-          const MrVec<T, V> a = MrVec<T, V>::ld(xs, i), b = MrVec<T, V>::ld(ys, i);
+          const Vec<T, V> a = Vec<T, V>::ld(xs, i), b = Vec<T, V>::ld(ys, i);
 #pragma unroll
           for (int e = 0; e < V; ++e) acc[e] += a.v[e] * b.v[e];
         }
@@ -176,8 +139,8 @@ __global__ void __launch_bounds__(MR_THREADS) k_minres_pass(const T* __restrict_
         const T* z1 = zring + (1 - cur) * GNK + seg;
         T* z2 = zring + cur * GNK + seg;
         for (long i = w.first; i < w.count; i += w.stride) {
-          const MrVec<T, V> p = MrVec<T, V>::ld(ps, i), a = MrVec<T, V>::ld(z1, i), b = MrVec<T, V>::ld(z2, i);
-          MrVec<T, V> z;
+          const Vec<T, V> p = Vec<T, V>::ld(ps, i), a = Vec<T, V>::ld(z1, i), b = Vec<T, V>::ld(z2, i);
+          Vec<T, V> z;
 #pragma unroll
           for (int e = 0; e < V; ++e) {
             z.v[e] = val * p.v[e] - al[e] * a.v[e] - bp[e] * b.v[e];
@@ -209,7 +172,7 @@ __global__ void __launch_bounds__(MR_THREADS) k_minres_pass(const T* __restrict_
           if (e >= ncol) continue;
           T s = sh[e][tid];
           for (int q = 1; q < MR_WAVES; ++q) s += sh[e][q * 64 + tid];
-          mr_st_agent(partial + ((long)g * K + w.col(K, V, e)) * nblk + blockIdx.x, s);
+          dpx_st_agent(partial + ((long)g * K + w.col(K, V, e)) * nblk + blockIdx.x, s);
         }
       }
     } else {                                                // the threads tid = j, j + KV, ... hold column group c
@@ -236,7 +199,7 @@ __global__ void __launch_bounds__(MR_THREADS) k_minres_pass(const T* __restrict_
           for (int e = 0; e < V; ++e) {
             T t = sh[e][tid];
             for (int q = 1; q < R; ++q) t += sh[e][q * w.KV + tid];
-            mr_st_agent(partial + ((long)g * K + tid * V + e) * nblk + blockIdx.x, t);
+            dpx_st_agent(partial + ((long)g * K + tid * V + e) * nblk + blockIdx.x, t);
           }
         }
       } else {
@@ -246,7 +209,7 @@ __global__ void __launch_bounds__(MR_THREADS) k_minres_pass(const T* __restrict_
           for (int e = 0; e < V; ++e) {
             T t = T(0);
             for (int q = j; q < MR_THREADS; q += w.KV) t += sh[e][q];
-            mr_st_agent(partial + ((long)g * K + c * V + e) * nblk + blockIdx.x, t);
+            dpx_st_agent(partial + ((long)g * K + c * V + e) * nblk + blockIdx.x, t);
           }
         }
       }
@@ -254,10 +217,7 @@ __global__ void __launch_bounds__(MR_THREADS) k_minres_pass(const T* __restrict_
     // stage two: the last workgroup of this leading system adds the partial sums and finishes the scalars
     if (!dpx_last_block(counter + g, (unsigned)nblk, &last)) continue;
     for (int c = wave; c < K; c += MR_WAVES) {
-      const T* pc = partial + ((long)g * K + c) * nblk;
-      double s = 0.0;
-      for (int i = lane; i < nblk; i += 64) s += (double)pc[i];
-      s = mr_wave_sum(s);
+      const double s = sum_partials_f64(partial + ((long)g * K + c) * nblk, nblk);
       if (lane == 0) {
         const long sys = (long)g * K + c;
         if constexpr (MODE == MR_DOT_ALPHA) st.alpha()[sys] = value * s;
@@ -304,19 +264,19 @@ __global__ void __launch_bounds__(MR_THREADS) k_minres_update(T* __restrict__ zr
       T* xs = sol + (long)s * GNK + seg;
       for (long i = w.first; i < w.count; i += w.stride) {
         if (s == 0) {
-          MrVec<T, V> zv = MrVec<T, V>::ld(z, i);
+          Vec<T, V> zv = Vec<T, V>::ld(z, i);
 #pragma unroll
           for (int e = 0; e < V; ++e) zv.v[e] /= bc[e];
           zv.st(z, i);
           if (qc) {
-            MrVec<T, V> cv = MrVec<T, V>::ld(qc + seg, i);
+            Vec<T, V> cv = Vec<T, V>::ld(qc + seg, i);
 #pragma unroll
             for (int e = 0; e < V; ++e) cv.v[e] /= bc[e];
             cv.st(qc + seg, i);
           }
         }
-        const MrVec<T, V> qv = MrVec<T, V>::ld(qs, i), a = MrVec<T, V>::ld(s1, i);
-        MrVec<T, V> b = MrVec<T, V>::ld(s2, i), xv = MrVec<T, V>::ld(xs, i);
+        const Vec<T, V> qv = Vec<T, V>::ld(qs, i), a = Vec<T, V>::ld(s1, i);
+        Vec<T, V> b = Vec<T, V>::ld(s2, i), xv = Vec<T, V>::ld(xs, i);
 #pragma unroll
         for (int e = 0; e < V; ++e) {
           b.v[e] = (qv.v[e] - sub[e] * a.v[e] - subsub[e] * b.v[e]) / diag[e];
@@ -348,7 +308,7 @@ __global__ void __launch_bounds__(MR_THREADS) k_minres_colscale(T* __restrict__ 
       zero[e] = mode == 2 && st.zero()[sys] != 0.0;
     }
     for (long i = w.first; i < w.count; i += w.stride) {
-      MrVec<T, V> v = MrVec<T, V>::ld(in + seg, i);
+      Vec<T, V> v = Vec<T, V>::ld(in + seg, i);
 #pragma unroll
       for (int e = 0; e < V; ++e) v.v[e] = mode == 2 ? (zero[e] ? T(0) : v.v[e] * c[e]) : v.v[e] / c[e];
       v.st(out + seg, i);
@@ -393,15 +353,14 @@ int mr_blocks(int G, long N, int K) {
   if (nb < floor_) nb = floor_;
   return (int)nb;
 }
-size_t mr_counter_bytes(int G) { return (((size_t)G + 1) * sizeof(unsigned) + 255) & ~(size_t)255; }
-bool mr_al16(const void* p) { return (size_t)p % 16 == 0; }
-// the vector length of a launch: 16 bytes when the layout and every buffer allow it
-template <class T> int mr_vec(long N, int K, std::initializer_list<const void*> bufs) {
+// the C ABI's is_f64 as the element type: f(double()) or f(float())
+template <class F> void mr_dispatch_type(int is_f64, F&& f) {
+  dispatch_flag(is_f64 != 0, [&](auto f64) { f(std::conditional_t<decltype(f64)::value, double, float>()); });
+}
+// the vector length of a launch as IntTag<V>: 16 bytes when the layout and every buffer (a null one does not object) allow it, or 1
+template <class T, class F> void mr_dispatch_vec(long N, int K, std::initializer_list<const void*> bufs, F&& f) {
   constexpr int V = 16 / sizeof(T);
-  if (!(K == 1 ? N % V == 0 : K % V == 0)) return 1;
-  for (const void* p : bufs)
-    if (!mr_al16(p)) return 1;
-  return V;
+  dispatch_flag((K == 1 ? N % V == 0 : K % V == 0) && aligned16(bufs), [&](auto vec) { f(IntTag<decltype(vec)::value ? V : 1>()); });
 }
 bool mr_shape_ok(const char* who, int S, int G, long N, int K) {
   if (S >= 1 && G >= 1 && N >= 1 && K >= 1 && (double)G * (double)N * (double)K * (double)S < 9.0e18) return true;
@@ -414,13 +373,11 @@ void mr_launch_pass(const void* x, const void* y, void* zring, const MrState& st
   const int nblk = mr_blocks(st.G, N, st.K);
   const dim3 grid(nblk, st.G < 65535 ? st.G : 65535, 1);
   unsigned* counter = (unsigned*)ws;
-  T* partial = (T*)((char*)ws + mr_counter_bytes(st.G));
-  if (mr_vec<T>(N, st.K, {x, y, zring}) > 1)
-    DPX_LAUNCH("k_minres_pass", (k_minres_pass<T, 16 / sizeof(T), MODE>), grid, dim3(MR_THREADS), 0, stream, (const T*)x, (const T*)y, (T*)zring, st, partial,
-               counter, N, value, eps, nblk);
-  else
-    DPX_LAUNCH("k_minres_pass", (k_minres_pass<T, 1, MODE>), grid, dim3(MR_THREADS), 0, stream, (const T*)x, (const T*)y, (T*)zring, st, partial, counter, N,
-               value, eps, nblk);
+  T* partial = (T*)((char*)ws + ticket_bytes(st.G + 1));
+  mr_dispatch_vec<T>(N, st.K, {x, y, zring}, [&](auto v) {
+    DPX_LAUNCH("k_minres_pass", (k_minres_pass<T, decltype(v)::value, MODE>), grid, dim3(MR_THREADS), 0, stream, (const T*)x, (const T*)y, (T*)zring, st,
+               partial, counter, N, value, eps, nblk);
+  });
 }
 
 template <class T>
@@ -428,21 +385,18 @@ void mr_launch_update(void* zring, const void* q, void* qc, void* search, void* 
   const int nblk = mr_blocks(st.G, N, st.K);
   const dim3 grid(nblk, st.G < 65535 ? st.G : 65535, 1);
   unsigned* ticket = (unsigned*)ws + st.G;
-  if (mr_vec<T>(N, st.K, {zring, q, qc, search, sol}) > 1)
-    DPX_LAUNCH("k_minres_update", (k_minres_update<T, 16 / sizeof(T)>), grid, dim3(MR_THREADS), 0, stream, (T*)zring, (const T*)q, (T*)qc, (T*)search, (T*)sol,
-               st, ticket, N, nblk);
-  else
-    DPX_LAUNCH("k_minres_update", (k_minres_update<T, 1>), grid, dim3(MR_THREADS), 0, stream, (T*)zring, (const T*)q, (T*)qc, (T*)search, (T*)sol, st, ticket,
-               N, nblk);
+  mr_dispatch_vec<T>(N, st.K, {zring, q, qc, search, sol}, [&](auto v) {
+    DPX_LAUNCH("k_minres_update", (k_minres_update<T, decltype(v)::value>), grid, dim3(MR_THREADS), 0, stream, (T*)zring, (const T*)q, (T*)qc, (T*)search,
+               (T*)sol, st, ticket, N, nblk);
+  });
 }
 
 template <class T> void mr_launch_colscale(void* out, const void* in, const MrState& st, int mode, long N, hipStream_t stream) {
   const int nblk = mr_blocks(st.G, N, st.K);
   const dim3 grid(nblk, st.G < 65535 ? st.G : 65535, 1);
-  if (mr_vec<T>(N, st.K, {out, in}) > 1)
-    DPX_LAUNCH("k_minres_colscale", (k_minres_colscale<T, 16 / sizeof(T)>), grid, dim3(MR_THREADS), 0, stream, (T*)out, (const T*)in, st, mode, N, nblk);
-  else
-    DPX_LAUNCH("k_minres_colscale", (k_minres_colscale<T, 1>), grid, dim3(MR_THREADS), 0, stream, (T*)out, (const T*)in, st, mode, N, nblk);
+  mr_dispatch_vec<T>(N, st.K, {out, in}, [&](auto v) {
+    DPX_LAUNCH("k_minres_colscale", (k_minres_colscale<T, decltype(v)::value>), grid, dim3(MR_THREADS), 0, stream, (T*)out, (const T*)in, st, mode, N, nblk);
+  });
 }
 
 }  // namespace
@@ -455,7 +409,7 @@ extern "C" size_t dpx_minres_state_bytes(int S, int G, int K) {
 
 extern "C" size_t dpx_minres_ws_bytes(int G, long N, int K) {
   if (G < 1 || N < 1 || K < 1) return 0;
-  return dpx::mr_counter_bytes(G) + (size_t)G * K * dpx::mr_blocks(G, N, K) * sizeof(double);
+  return dpx::ticket_bytes(G + 1) + (size_t)G * K * dpx::mr_blocks(G, N, K) * sizeof(double);
 }
 
 extern "C" int dpx_minres_init(void* state, int phase, int S, int G, int K, dpx_stream_t stream) {
@@ -474,8 +428,7 @@ extern "C" int dpx_minres_colscale(void* out, const void* in, void* state, int m
   DPX_REQUIRE(mode >= 0 && mode <= 2, "dpx_minres_colscale: mode %d (0 .. 2)", mode);
   if (!mr_shape_ok("dpx_minres_colscale", S, G, N, K)) return DPX_ERR_ARG;
   const MrState st{(double*)state, S, G, K};
-  if (is_f64) mr_launch_colscale<double>(out, in, st, mode, N, (hipStream_t)stream);
-  else mr_launch_colscale<float>(out, in, st, mode, N, (hipStream_t)stream);
+  mr_dispatch_type(is_f64, [&](auto t) { mr_launch_colscale<decltype(t)>(out, in, st, mode, N, (hipStream_t)stream); });
   return launch_status("dpx_minres_colscale");
 }
 
@@ -485,8 +438,7 @@ extern "C" int dpx_minres_alpha(const void* prod, const void* q, const void* zri
   DPX_REQUIRE(prod && (q || zring) && state && ws, "dpx_minres_alpha: null pointer");
   if (!mr_shape_ok("dpx_minres_alpha", S, G, N, K)) return DPX_ERR_ARG;
   const MrState st{(double*)state, S, G, K};
-  if (is_f64) mr_launch_pass<double, MR_DOT_ALPHA>(prod, q, (void*)zring, st, ws, N, value, 0.0, (hipStream_t)stream);
-  else mr_launch_pass<float, MR_DOT_ALPHA>(prod, q, (void*)zring, st, ws, N, value, 0.0, (hipStream_t)stream);
+  mr_dispatch_type(is_f64, [&](auto t) { mr_launch_pass<decltype(t), MR_DOT_ALPHA>(prod, q, (void*)zring, st, ws, N, value, 0.0, (hipStream_t)stream); });
   return launch_status("dpx_minres_alpha");
 }
 
@@ -497,13 +449,10 @@ extern "C" int dpx_minres_lanczos(const void* prod, void* zring, double value, d
   if (!mr_shape_ok("dpx_minres_lanczos", S, G, N, K)) return DPX_ERR_ARG;
   const MrState st{(double*)state, S, G, K};
   const hipStream_t s = (hipStream_t)stream;
-  if (is_f64) {
-    if (finish) mr_launch_pass<double, MR_LANCZOS>(prod, nullptr, zring, st, ws, N, value, eps, s);
-    else mr_launch_pass<double, MR_LANCZOS_PLAIN>(prod, nullptr, zring, st, ws, N, value, eps, s);
-  } else {
-    if (finish) mr_launch_pass<float, MR_LANCZOS>(prod, nullptr, zring, st, ws, N, value, eps, s);
-    else mr_launch_pass<float, MR_LANCZOS_PLAIN>(prod, nullptr, zring, st, ws, N, value, eps, s);
-  }
+  mr_dispatch_type(is_f64, [&](auto t) {
+    if (finish) mr_launch_pass<decltype(t), MR_LANCZOS>(prod, nullptr, zring, st, ws, N, value, eps, s);
+    else mr_launch_pass<decltype(t), MR_LANCZOS_PLAIN>(prod, nullptr, zring, st, ws, N, value, eps, s);
+  });
   return launch_status("dpx_minres_lanczos");
 }
 
@@ -513,8 +462,7 @@ extern "C" int dpx_minres_beta(const void* zring, const void* qc, double eps, vo
   DPX_REQUIRE(zring && qc && state && ws, "dpx_minres_beta: null pointer");
   if (!mr_shape_ok("dpx_minres_beta", S, G, N, K)) return DPX_ERR_ARG;
   const MrState st{(double*)state, S, G, K};
-  if (is_f64) mr_launch_pass<double, MR_DOT_BETA>(nullptr, qc, (void*)zring, st, ws, N, 1.0, eps, (hipStream_t)stream);
-  else mr_launch_pass<float, MR_DOT_BETA>(nullptr, qc, (void*)zring, st, ws, N, 1.0, eps, (hipStream_t)stream);
+  mr_dispatch_type(is_f64, [&](auto t) { mr_launch_pass<decltype(t), MR_DOT_BETA>(nullptr, qc, (void*)zring, st, ws, N, 1.0, eps, (hipStream_t)stream); });
   return launch_status("dpx_minres_beta");
 }
 
@@ -524,7 +472,6 @@ extern "C" int dpx_minres_update(void* zring, const void* q, void* qc, void* sea
   DPX_REQUIRE(zring && search && solution && state && ws, "dpx_minres_update: null pointer");
   if (!mr_shape_ok("dpx_minres_update", S, G, N, K)) return DPX_ERR_ARG;
   const MrState st{(double*)state, S, G, K};
-  if (is_f64) mr_launch_update<double>(zring, q, qc, search, solution, st, ws, N, (hipStream_t)stream);
-  else mr_launch_update<float>(zring, q, qc, search, solution, st, ws, N, (hipStream_t)stream);
+  mr_dispatch_type(is_f64, [&](auto t) { mr_launch_update<decltype(t)>(zring, q, qc, search, solution, st, ws, N, (hipStream_t)stream); });
   return launch_status("dpx_minres_update");
 }

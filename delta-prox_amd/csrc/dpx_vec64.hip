@@ -5,35 +5,9 @@
 // test_linear_solver_torch.py:33-57).  The hot path of this backend is float32; these kernels let the same solvers keep a float64
 // right-hand side in float64 on the device instead of rounding it: batched dots and the B x B Gram matrix (deterministic: per-block
 // partials + a finishing pass, no atomics), linear combinations, and max |x| -- for float32 and float64.
-#include "dpx_common.h"
+#include "dpx_reduce_dev.h"
 
 namespace dpx {
-
-template <class T> __device__ __forceinline__ T wave_sum_t(T v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-template <class T> __device__ __forceinline__ T wave_max_t(T v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const T w = __shfl_xor(v, o);
-    v = w > v ? w : v;
-  }
-  return v;
-}
-// sum (MAX = false) or maximum over the block; valid in thread 0
-template <class T, bool MAX> __device__ __forceinline__ T block_reduce_t(T v, T* sh) {
-  v = MAX ? wave_max_t(v) : wave_sum_t(v);
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  __syncthreads();
-  if (lane == 0) sh[wid] = v;
-  __syncthreads();
-  const int nw = (blockDim.x + 63) >> 6;
-  T r = (threadIdx.x < nw) ? sh[threadIdx.x] : T(0);
-  if (wid == 0) r = MAX ? wave_max_t(r) : wave_sum_t(r);
-  return r;
-}
 
 // grid (nblk, B, Bj): partial[(bi * Bj + bj) * nblk + blk] = sum over a slice of <x[bi], y[gram ? bj : bi]>
 __global__ void k_dot_partial_f64(const double* __restrict__ x, const double* __restrict__ y, double* __restrict__ partial, long npb, int gram) {
@@ -43,14 +17,14 @@ __global__ void k_dot_partial_f64(const double* __restrict__ x, const double* __
   const double* yb = y + (long)bj * npb;
   double acc = 0.0;
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < npb; i += (long)gridDim.x * blockDim.x) acc = fma(xa[i], yb[i], acc);
-  acc = block_reduce_t<double, false>(acc, sh);
+  acc = block_sum(acc, sh);
   if (threadIdx.x == 0) partial[((long)bi * gridDim.z + blockIdx.z) * gridDim.x + blockIdx.x] = acc;
 }
 __global__ void k_sum_finish_f64(const double* __restrict__ partial, double* __restrict__ out, int nblk) {
   __shared__ double sh[16];
   double acc = 0.0;
   for (int i = threadIdx.x; i < nblk; i += blockDim.x) acc += partial[(long)blockIdx.x * nblk + i];
-  acc = block_reduce_t<double, false>(acc, sh);
+  acc = block_sum(acc, sh);
   if (threadIdx.x == 0) out[blockIdx.x] = acc;
 }
 
@@ -81,7 +55,7 @@ template <class T> __global__ void k_absmax(const T* __restrict__ x, T* __restri
     const T a = x[i] < T(0) ? -x[i] : x[i];
     m = a > m ? a : m;
   }
-  m = block_reduce_t<T, true>(m, sh);
+  m = block_sum<T, true>(m, sh);
   if (threadIdx.x == 0) out[blockIdx.x] = m;
 }
 

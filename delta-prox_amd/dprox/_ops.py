@@ -359,43 +359,32 @@ def absmax(x):
     return out
 
 
+def _f64_or_f32(t):
+    """(element type, C symbol suffix, workspace tag) of the float64 or the float32 dot / Gram kernels"""
+    return (torch.float64, "_f64", "dot64") if t.dtype == torch.float64 else (torch.float32, "", "dot")
+
+
 def bdot(x, y):
-    if x.dtype == torch.float64:
-        require(x, dtype=torch.float64, what="bdot x"), require(y, dtype=torch.float64, what="bdot y")
-        B = int(x.shape[0])
-        npb = x.numel() // B
-        L = be.lib()
-        out = torch.empty(B, dtype=torch.float64, device=x.device)
-        ws = workspace("dot64", L.query("dpx_bdot_f64_ws_bytes", B, npb), x.device)
-        L.call("dpx_bdot_f64", ptr(x), ptr(y), ptr(out), B, npb, ptr(ws), be.stream())
-        return out
-    require(x, what="bdot x"), require(y, what="bdot y")
+    dtype, sfx, tag = _f64_or_f32(x)
+    require(x, dtype=dtype, what="bdot x"), require(y, dtype=dtype, what="bdot y")
     B = int(x.shape[0])
     npb = x.numel() // B
     L = be.lib()
-    out = torch.empty(B, dtype=torch.float32, device=x.device)
-    ws = workspace("dot", L.query("dpx_bdot_ws_bytes", B, npb), x.device)
-    L.call("dpx_bdot", ptr(x), ptr(y), ptr(out), B, npb, ptr(ws), be.stream())
+    out = torch.empty(B, dtype=dtype, device=x.device)
+    ws = workspace(tag, L.query(f"dpx_bdot{sfx}_ws_bytes", B, npb), x.device)
+    L.call(f"dpx_bdot{sfx}", ptr(x), ptr(y), ptr(out), B, npb, ptr(ws), be.stream())
     return out
 
 
 def bgram(r):
-    if r.dtype == torch.float64:
-        require(r, dtype=torch.float64, what="bgram r")
-        B = int(r.shape[0])
-        npb = r.numel() // B
-        L = be.lib()
-        out = torch.empty(B, B, dtype=torch.float64, device=r.device)
-        ws = workspace("dot64", L.query("dpx_bdot_f64_ws_bytes", B, npb), r.device)
-        L.call("dpx_bgram_f64", ptr(r), ptr(out), B, npb, ptr(ws), be.stream())
-        return out
-    require(r, what="bgram r")
+    dtype, sfx, tag = _f64_or_f32(r)
+    require(r, dtype=dtype, what="bgram r")
     B = int(r.shape[0])
     npb = r.numel() // B
     L = be.lib()
-    out = torch.empty(B, B, dtype=torch.float32, device=r.device)
-    ws = workspace("dot", L.query("dpx_bdot_ws_bytes", B, npb), r.device)
-    L.call("dpx_bgram", ptr(r), ptr(out), B, npb, ptr(ws), be.stream())
+    out = torch.empty(B, B, dtype=dtype, device=r.device)
+    ws = workspace(tag, L.query(f"dpx_bdot{sfx}_ws_bytes", B, npb), r.device)
+    L.call(f"dpx_bgram{sfx}", ptr(r), ptr(out), B, npb, ptr(ws), be.stream())
     return out
 
 

@@ -703,6 +703,85 @@ def case_cg_branches(device, quick=False):
         L.call("dpx_cg_config", old[0], old[1], old[2])
 
 
+def case_cg_control_forms(device):
+    """dpx_cg_direction and dpx_cg_update, called directly through ops.CgControl, in both forms of their kernels: 16-byte accesses
+    (n_per_batch a multiple of 4, every buffer 16-byte aligned) and element by element (any other length or alignment).  B = 3 systems.
+
+    Bounds, eps32 = 2^-23, everything on the right-hand sides from the float64 restatement:
+      direction  p = r + beta p, one fused multiply-add per element: eps32 (|beta p| + |r|)
+      <p, Ap>    a dot product over npb elements (tests/minres_cases.py): (sqrt(npb) + 4) eps32 sum |p Ap|
+      update     alpha = gamma / pAp in float64 from the DEVICE's pAp; x within eps32 (|x| + 3 |alpha p|), r within
+                 eps32 (|r| + 3 |alpha Ap|): one rounding each for the device's float32 division, the product and the sum
+    With the same values the two forms apply the same fused multiply-add to every element: their p, x and r are bit-identical.
+    A frozen solve (flags()[0] = 1) leaves every operand untouched in both forms."""
+    from dprox import _ops as ops
+    B, eps32 = 3, float(np.finfo(np.float32).eps)
+    rng = np.random.RandomState(20)
+    beta, gamma, gamma_prev = np.float32([0.37, -1.25, 2.5]), np.float32([1.7, 0.45, -0.8]), np.float32([0.9, 1.1, 1.3])
+    f64 = lambda t: t.detach().cpu().numpy().astype(np.float64)
+
+    def fresh(a):                                        # a fresh allocation (on the CPU T() shares the array's memory): 16-byte aligned
+        t = T(a, device).clone()
+        assert t.data_ptr() % 16 == 0
+        return t
+
+    def shifted(a):                                      # the same values in a contiguous view 4 bytes into a larger allocation
+        t = torch.empty(a.size + 1, dtype=torch.float32, device=device)[1:].view(a.shape)
+        t.copy_(T(a, device))
+        assert t.data_ptr() % 16 == 4 and t.is_contiguous()
+        return t
+
+    def run(v, place, frozen, what):
+        npb = v["p"].shape[1]
+        ctl = ops.CgControl(fresh(v["b"]), 1e-6)
+        for i, s in enumerate((gamma, gamma_prev, beta)):         # the state block's layout (dpx_cg_dev.h): gamma, gamma_prev, beta, pAp, tol2
+            ctl.state[i * B:(i + 1) * B].copy_(T(s, device))
+        if frozen:
+            ctl.flags[0:1].fill_(1)
+        p, r, x, Ap = (place(v[k]) for k in ("p", "r", "x", "Ap"))
+        ctl.direction(p, r)
+        p_dev = p.clone()
+        ctl.update(x, r, p, Ap)
+        out = {"p": p_dev.cpu().numpy(), "p_end": p.cpu().numpy(), "x": x.cpu().numpy(), "r": r.cpu().numpy(), "Ap": Ap.cpu().numpy()}
+        if frozen:
+            for k, src in (("p", "p"), ("p_end", "p"), ("x", "x"), ("r", "r"), ("Ap", "Ap")):
+                assert np.array_equal(out[k], v[src]), (what, "frozen solve", k)
+            return out
+        b64 = beta.astype(np.float64)[:, None]
+        p0, r0, x0, q = (v[k].astype(np.float64) for k in ("p", "r", "x", "Ap"))
+        worst = {}
+
+        def within(name, got, ref, bound):
+            ratio = float(np.max(np.abs(got.astype(np.float64) - ref) / bound))
+            worst[name] = ratio
+            print(f"case_cg_control_forms {what}: {name} error / bound = {ratio:.3f}")
+            assert ratio <= 1.0, (what, name, ratio)
+
+        within("direction", out["p"], r0 + b64 * p0, eps32 * (np.abs(b64 * p0) + np.abs(r0)))
+        assert np.array_equal(out["p_end"], out["p"]) and np.array_equal(out["Ap"], v["Ap"]), what
+        pd = out["p"].astype(np.float64)
+        pAp = f64(ctl.pAp)
+        within("pAp", pAp, np.sum(pd * q, axis=1), (np.sqrt(npb) + 4.0) * eps32 * np.sum(np.abs(pd * q), axis=1))
+        alpha = (gamma.astype(np.float64) / pAp)[:, None]
+        within("x", out["x"], x0 + alpha * pd, eps32 * (np.abs(x0) + 3 * np.abs(alpha * pd)))
+        within("r", out["r"], r0 - alpha * q, eps32 * (np.abs(r0) + 3 * np.abs(alpha * q)))
+        record(f"cg control forms, {what}: largest error / bound", max(worst.values()), 1.0)
+        return out
+
+    for npb in (5, 8):
+        v = {k: rng.randn(B, npb).astype(np.float32) for k in ("b", "p", "r", "x", "Ap")}
+        if npb % 4:                                      # element by element whatever the alignment
+            run(v, fresh, False, f"npb={npb}")
+            run(v, fresh, True, f"npb={npb}")
+            continue
+        a = run(v, fresh, False, f"npb={npb}, 16-byte aligned")
+        s = run(v, shifted, False, f"npb={npb}, 4 bytes off")
+        for k in ("p", "x", "r"):
+            assert np.array_equal(a[k], s[k]), (npb, "16-byte and element-wise forms differ", k)
+        run(v, fresh, True, f"npb={npb}, 16-byte aligned")
+        run(v, shifted, True, f"npb={npb}, 4 bytes off")
+
+
 def case_cg_wave_fft(device, sizes=(320, 384), B=3, iters=6):
     """the fused CG matvec on 320 x 320 and 384 x 384 planes -- every 1-D transform on one wave's registers (k_crows_real_in_w,
     k_ccols_mask_w, k_crows_real_out_w: radix 5 / 6, 8, 8) -- against the size-generic kernels (knob cg_wave_fft = 2, themselves pinned

@@ -116,6 +116,10 @@ def test_cg_both_branches_of_the_fused_call():
     pc.case_cg_branches(DEV, quick=True)
 
 
+def test_cg_control_kernels_in_both_forms():
+    pc.case_cg_control_forms(DEV)
+
+
 def test_cg_matvec_with_one_wave_transforms_320():
     pc.case_cg_wave_fft(DEV, sizes=(320,), B=1, iters=3)
 

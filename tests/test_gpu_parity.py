@@ -129,6 +129,11 @@ def test_cg_both_branches_of_the_fused_call():
     pc.case_cg_branches(DEV)
 
 
+@pytest.mark.gpu
+def test_cg_control_kernels_in_both_forms():
+    pc.case_cg_control_forms(DEV)
+
+
 def test_cg_matvec_with_one_wave_transforms_320_384():
     pc.case_cg_wave_fft(DEV)
 

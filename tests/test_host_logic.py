@@ -166,6 +166,69 @@ def test_cross_file_internals_are_declared_once_in_dpx_internal_h():
     assert not faults, "\n".join(faults)
 
 
+# Full-wave butterflies left open-coded: replacing the loop by the call changes the kernel's assembly (instruction order, or the count),
+# and these kernels are on benchmarked paths (profiles/reduce_helpers_isa.txt).  file -> (loop headers, reason)
+_BUTTERFLY_LOOPS_KEPT = {
+    "dpx_reduce_dev.h": (2, "wave_sum and wave_max themselves"),
+    "dpx_fft.hip": (4, "k_crows_real_out and k_crows_real_out_w<5>, <6>: same instructions in another order at both sites of each kernel"),
+    "dpx_bwd_rows_par.hip": (1, "k_bwd_rows_par reduces two doubles in one loop to keep register pressure down: all 24 instantiations change"),
+    "dpx_conv_bf16.hip": (1, "k_bx_absmax: fmaxf butterfly, 204 -> 213 instructions with wave_max's comparison form"),
+}
+_REDUCE_NAMES = r"\w*(?:wave_sum|wave_max|block_sum|block_reduce|st_agent|al16|aligned16)\w*"
+
+
+def _reduce_helper_faults(csrc):
+    """what test_reduction_helpers_are_written_once_in_dpx_reduce_dev_h rejects in a csrc/ directory, one line each"""
+    faults = []
+    if not os.path.exists(os.path.join(csrc, "dpx_reduce_dev.h")):
+        faults.append("dpx_reduce_dev.h is missing")
+    for f in sorted(os.listdir(csrc)):
+        if not f.endswith((".hip", ".h")):
+            continue
+        text = _strip_comments_and_strings(open(os.path.join(csrc, f)).read())
+        line = lambda m: text.count("\n", 0, m.start()) + 1
+        if f != "dpx_reduce_dev.h":
+            # a function definition (a type or a declarator in front of the name, a parameter list, a body), a lambda, a function-like macro
+            for m in re.finditer(r"(\w+|[>*&])\s+(%s)\s*\([^;{}()]*(?:\([^()]*\)[^;{}()]*)*\)\s*(?:const\s*)?\{" % _REDUCE_NAMES, text):
+                if m.group(1) not in ("return", "else", "case", "new", "throw"):
+                    faults.append(f"{f}:{line(m)}: defines {m.group(2)}")
+            for m in re.finditer(r"\b(%s)\s*=\s*\[[^\]\n]*\]\s*\(" % _REDUCE_NAMES, text):
+                faults.append(f"{f}:{line(m)}: defines the lambda {m.group(1)}")
+            for m in re.finditer(r"^[ \t]*#[ \t]*define[ \t]+(%s)\(" % _REDUCE_NAMES, text, re.M):
+                faults.append(f"{f}:{line(m)}: defines the macro {m.group(1)}")
+        loops = list(re.finditer(r"\bfor\s*\(\s*int\s+o\s*=\s*32\s*;\s*o\s*>\s*0\s*;\s*o\s*>>=\s*1\s*\)", text))
+        kept = _BUTTERFLY_LOOPS_KEPT.get(f, (0, ""))[0]
+        if len(loops) != kept:
+            faults += [f"{f}:{line(m)}: open-coded full-wave butterfly ({len(loops)} in the file, {kept} listed)" for m in loops] or \
+                      [f"{f}: no open-coded butterfly left, {kept} listed"]
+    return faults
+
+
+def test_reduction_helpers_are_written_once_in_dpx_reduce_dev_h():
+    """The wave butterflies, the block-level sum, the write-through store of the last-workgroup hand-over and the 16-byte alignment test
+    live in csrc/dpx_reduce_dev.h and nowhere else: no other file of csrc/ defines a function, lambda or macro whose name contains
+    wave_sum, wave_max, block_sum, block_reduce, st_agent, al16 or aligned16, and the butterfly's loop header appears only in that header
+    and at the sites _BUTTERFLY_LOOPS_KEPT lists with their reason (exactly as many as listed: a site that goes is taken off the list)."""
+    import tempfile
+    with tempfile.TemporaryDirectory() as d:              # the checker finds each kind of copy, and only those
+        open(os.path.join(d, "dpx_reduce_dev.h"), "w").write(
+            "template <class T> T wave_sum(T v) {\n  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);\n  for (int o = 32; o > 0; o >>= 1) v = v;\n}\n")
+        open(os.path.join(d, "dpx_probe.hip"), "w").write(
+            "// float my_wave_sum(float v) { in a comment }\n"
+            "__device__ __forceinline__ float my_wave_sum(float v) {\n  for (int o = 32;  o > 0; o >>= 1) v += __shfl_xor(v, o);\n  return v;\n}\n"
+            "template <class T, bool MAX> __device__ T block_reduce_t(T v, T* sh) { return v; }\n"
+            "static bool mr_al16(const void* p) { return (size_t)p % 16 == 0; }\n"
+            "void user(float* p) {\n  auto wave_sum_d = [](double v) { return v; };\n  const bool al16 = aligned16({p});\n"
+            "  if (aligned16({p}) && wave_sum(p[0]) > 0) { p[0] = block_sum(p[0], p); }\n  for (int o = 32; o >= KV; o >>= 1) p[o] = 0;\n}\n"
+            "#define st_agent_all(p) (p)\n")
+        got = _reduce_helper_faults(d)
+    assert [g.split(": ", 1)[1].split(" (")[0] for g in got] == [
+        "defines my_wave_sum", "defines block_reduce_t", "defines mr_al16", "defines the lambda wave_sum_d", "defines the macro st_agent_all",
+        "open-coded full-wave butterfly"], got
+    faults = _reduce_helper_faults(os.path.join(ROOT, "delta-prox_amd", "csrc"))
+    assert not faults, "\n".join(faults)
+
+
 def test_wheel_builds_and_imports_without_path_edits(tmp_path):
     """packaging (pyproject.toml + setup.py): `pip wheel` runs the HIP build hook, the wheel holds the package `dprox` with
     dprox/lib/libdpx_hip.so inside, and a fresh interpreter imports it from the unpacked wheel alone (no sys.path edits, no repo)"""
