@@ -1154,3 +1154,52 @@ def nlm(v, sigma, search=11, patch=5):
     out = torch.empty_like(v)
     be.lib().call("dpx_nlm", ptr(v), ptr(out), ptr(sig), B, C, H, W, int(search), int(patch), be.stream())
     return out
+
+
+def _tv_axes_mask(axes):
+    """NCHW dims out of {1, 2, 3} -> dpx_tv_denoise's bit mask (bit 0 = dim 1)"""
+    try:
+        dims = tuple(axes)
+    except TypeError:
+        raise be.DpxError(f"tv_denoise: axes {axes!r} (a tuple of NCHW dims out of 1, 2, 3)")
+    if not dims or len(set(dims)) != len(dims) or any(isinstance(d, bool) or int(d) != d or d not in (1, 2, 3) for d in dims):
+        raise be.DpxError(f"tv_denoise: axes {axes!r} (a non-empty tuple of distinct NCHW dims out of 1, 2, 3)")
+    return sum(1 << (int(d) - 1) for d in dims)
+
+
+def tv_plan(shape, iters=5, axes=(1, 2)):
+    """what dpx_tv_denoise would do on an [N, C, H, W] volume: dict(steps, launches, tile, lds_bytes) (dpx_tv_plan)"""
+    _, D0, D1, D2 = (int(n) for n in shape)
+    out = (ctypes.c_int * 6)()
+    be.lib().call("dpx_tv_plan", D0, D1, D2, _tv_axes_mask(axes), int(iters), out)
+    return dict(steps=out[0], launches=out[1], tile=(out[2], out[3], out[4]), lds_bytes=out[5])
+
+
+def tv_denoise(v, lam, iters=5, axes=(1, 2)):
+    """anisotropic TV denoising of an [N, C, H, W] fp32 volume: `iters` projected dual-ascent steps (step 1/5, threshold lam / 2) with
+    differences along the NCHW dims in `axes` -- the reference's TV_denoising ((1, 2): its 2-D form differences C and H) / TV_denoising3d
+    ((1, 2, 3)) in one dpx_tv_denoise call; lam: per-image (0-d / [N]), >= 0 (checked where it is a host value; a device tensor is not
+    read back); forward-only; a new tensor"""
+    if not isinstance(v, torch.Tensor):
+        raise be.DpxError(f"tv_denoise: expected a torch.Tensor, got {type(v)}")
+    if v.is_complex() or v.dtype != torch.float32:
+        raise be.DpxError(f"tv_denoise: expected a real float32 volume, got {v.dtype}")
+    if torch.is_grad_enabled() and (v.requires_grad or (isinstance(lam, torch.Tensor) and lam.requires_grad)):
+        raise NotImplementedError("tv_denoise is forward-only: it has no backward kernel (the reference differentiates through its "
+                                  "TV steps); call it under torch.no_grad()")
+    N, D0, D1, D2 = _shape4(v)
+    if min(N, D0, D1, D2) < 1:
+        raise be.DpxError(f"tv_denoise: empty volume {tuple(v.shape)}")
+    mask = _tv_axes_mask(axes)
+    if int(iters) != iters or iters < 1:
+        raise be.DpxError(f"tv_denoise: iters {iters} (an integer >= 1)")
+    host_lam = lam if not isinstance(lam, torch.Tensor) else (lam.detach() if lam.device.type == "cpu" else None)
+    if host_lam is not None and bool((torch.as_tensor(host_lam) < 0).any()):
+        raise be.DpxError("tv_denoise: lam must be >= 0")
+    v = require(v.contiguous(), what="tv_denoise input")
+    lam = as_batch_vec(lam, N, v.device)            # (held until the call returns)
+    L = be.lib()
+    ws = workspace("tv", L.query("dpx_tv_ws_bytes", N, D0, D1, D2, mask, int(iters)), v.device)
+    out = torch.empty_like(v)
+    L.call("dpx_tv_denoise", ptr(v), ptr(out), ptr(lam), N, D0, D1, D2, mask, int(iters), ptr(ws), be.stream())
+    return out

@@ -3,7 +3,7 @@
 ``plan_admm`` pattern-matches the compiled problem:
 
     Omega : sum_squares( conv(x, psf) - b )  |  sum_squares( x - b )          (any number)
-    Psi   : norm1 / norm2 / nonneg / deep_prior(FFDNet) / patch_nlm  of  x | grad(x, 0) | grad(x, 1)   (<= 4 terms; the last two on x)
+    Psi   : norm1 / norm2 / nonneg / deep_prior(FFDNet | TVDenoiser) / patch_nlm  of  x | grad(x, 0) | grad(x, 1)   (<= 4 terms; the last two on x)
 
 and replaces the reference's per-iteration graph walks (dprox/algo/admm.py:49-59 ->
 proxfn/sum_square.py:123-156 -> linop/comp_graph.py:198-282; 18 full complex FFTs and ~80 eager ops
@@ -31,7 +31,7 @@ from . import autodiff
 from ..linop import Constant, Variable, conv, conv_doe, grad
 from ..linop import sum as lin_sum
 from ..proxfn import deep_prior, least_squares, nonneg, norm1, norm2, patch_nlm, sum_squares
-from ..proxfn.pnp.denoisers import Denoiser2D, FFDNetColorDenoiser, FFDNetDenoiser
+from ..proxfn.pnp.denoisers import Denoiser2D, FFDNetColorDenoiser, FFDNetDenoiser, TVDenoiser
 
 
 def _is_var(op):
@@ -85,7 +85,7 @@ def _psi_prox_code(fn):
         return be.PROX_NONNEG
     if type(fn) is norm2:
         return be.PROX_SUMSQ
-    if type(fn) is deep_prior and not fn.unroll and not fn.clamp and isinstance(fn.denoiser, (FFDNetColorDenoiser, FFDNetDenoiser)):
+    if type(fn) is deep_prior and not fn.unroll and not fn.clamp and isinstance(fn.denoiser, (FFDNetColorDenoiser, FFDNetDenoiser, TVDenoiser)):
         return be.PROX_EXTERNAL
     if type(fn) is patch_nlm:
         return be.PROX_EXTERNAL
@@ -236,11 +236,13 @@ def _sigma_table(fn, lt):
 
 
 def _denoise_split(fn, d, sig):
-    """z-update of a deep_prior / patch_nlm term: v = D(d; sigma) with d = x + u (the denoiser's own HIP kernels; dpx_nlm)"""
+    """z-update of a deep_prior / patch_nlm term: v = D(d; sigma) with d = x + u (the denoiser's own HIP kernels; dpx_tv_denoise; dpx_nlm)"""
     if isinstance(fn, patch_nlm):
         return ops.nlm(d, sig, fn.search_window_size, fn.patch_size)
     B, C, H, W = d.shape
     den = fn.denoiser
+    if isinstance(den, TVDenoiser):
+        return ops.tv_denoise(d, sig, den.iter_num, den.dims)
     if isinstance(den, Denoiser2D):
         return den.model(d.reshape(B * C, 1, H, W), sig.repeat_interleave(C) if C > 1 else sig).reshape(B, C, H, W)
     return den.model(d, sig)
@@ -701,7 +703,8 @@ class FusedADMM:
             for i in ext:                                            # v_i holds d = x + u_i
                 d = v[i]
                 out = _denoise_split(psi[i], d, lam_tab[i][it])
-                ops.lincomb([(1.0, d), (-1.0, out)], out=u[i])       # u_i = d - v_i
+                if dual:                                             # (half-quadratic splitting: the duals stay zero)
+                    ops.lincomb([(1.0, d), (-1.0, out)], out=u[i])   # u_i = d - v_i
                 v[i] = out
                 terms[i].v = out.data_ptr()
             var.value = x

@@ -15,6 +15,7 @@ from .. import _ops as ops
 from ..linalg import LinearSolveConfig
 from ..linop import Variable, adjoint, eval
 from ..proxfn import ProxFn, ext_sum_squares, least_squares, sum_squares
+from ..proxfn.pnp.denoisers import TVDenoiser
 from .driver import Algorithm, expand
 from . import fused
 
@@ -145,11 +146,15 @@ class LinearizedADMM(ADMM):
         return x, v, u
 
 
-def _fused_closed_form(solver, state, rhos, lams):
-    """the fused ADMM's plan when every Psi prox is closed-form and no gradient is requested, else None"""
+def _fused_closed_form(solver, state, rhos, lams, denoisers=()):
+    """the fused ADMM's plan when every Psi prox is closed-form (or a deep_prior whose denoiser is one of `denoisers`) and no gradient
+    is requested, else None"""
     plan = fused.plan_admm(solver, state) if solver.use_fused else None
-    if plan is None or len(state[1]) == 0 or any(pc == fused.be.PROX_EXTERNAL for _, pc in plan.codes):
+    if plan is None or len(state[1]) == 0:
         return None
+    for fn, (_, pc) in zip(solver.psi_fns, plan.codes):
+        if pc == fused.be.PROX_EXTERNAL and not (denoisers and isinstance(getattr(fn, "denoiser", None), denoisers)):
+            return None
     tensors = [state[0], rhos] + list(lams.values()) + [t for part in state[1:] for t in (part if isinstance(part, (list, tuple)) else [part])]
     if torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in tensors):
         return None
@@ -187,9 +192,9 @@ class HQS(ADMM):
         return x, [e if e is not x else e.clone() for e in z]
 
     def iters(self, state, rhos, lams, max_iter, pbar=False, callback=None):
-        """recognised problems (the fused ADMM's criteria, closed-form proxes only, no gradients requested) run the fused
-        rhs / Fourier-solve / z stages with the dual variables pinned to zero; everything else op by op"""
-        plan = _fused_closed_form(self, state, rhos, lams)
+        """recognised problems (the fused ADMM's criteria, closed-form proxes and the TV denoiser prior only, no gradients requested)
+        run the fused rhs / Fourier-solve / z stages with the dual variables pinned to zero; everything else op by op"""
+        plan = _fused_closed_form(self, state, rhos, lams, denoisers=(TVDenoiser,))
         if plan is not None:
             self.last_path = "fused"
             return plan.run(state, rhos, lams, max_iter, pbar, callback, dual=False)

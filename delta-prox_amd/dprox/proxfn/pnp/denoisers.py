@@ -50,6 +50,37 @@ class Denoiser2D(Denoiser):
         return out
 
 
+class TVDenoiser(Denoiser):
+    """Anisotropic total-variation denoiser without weights (reference denoisers/wrapper.py:8-22 over models/TV_denoising.py):
+    ``iter_num`` projected dual-ascent steps at threshold ``sigma / 2``, one ``dpx_tv_denoise`` call (``ops.tv_denoise``; the
+    reference runs ~15 eager ops per step).
+
+    Which axes: the reference squeezes ``[1, C, H, W]`` to ``[C, H, W]``, so its 2-D form differences **C and H** (NCHW dims 1, 2),
+    not H and W, and its 3-D form (``use_3dtv=True``) C, H and W.  That is the default here too.  Extensions over the reference:
+    ``dims`` -- a tuple out of NCHW dims {1, 2, 3} -- selects the differenced axes itself (``dims=(2, 3)`` is the per-plane spatial TV
+    of RGB / gray images) and overrides ``use_3dtv``; batches of N > 1 images with a per-image ``sigma`` ([N] or 0-d: the reference
+    raises on N > 1); a differenced axis of length 1 contributes no differences but still counts in the mean over the axes (the
+    reference returns an empty tensor).  ``sigma`` must be >= 0; ``sigma = 0`` returns the input bit for bit.  The denoiser is
+    forward-only: a call that autograd would have to differentiate raises NotImplementedError (the reference does differentiate
+    through its TV steps; there is no backward kernel here yet)."""
+
+    def __init__(self, iter_num=5, use_3dtv=False, dims=None):
+        super().__init__()
+        self.iter_num = int(iter_num)
+        self.use_3dtv = bool(use_3dtv)
+        if dims is None:
+            dims = (1, 2, 3) if self.use_3dtv else (1, 2)
+        ops._tv_axes_mask(dims)                          # (raises on anything but a set of NCHW dims out of 1, 2, 3)
+        self.dims = tuple(int(d) for d in dims)
+
+    def denoise(self, input, sigma):
+        """input: [N, C, H, W]; sigma: 0-d or [N]"""
+        return ops.tv_denoise(input, sigma, self.iter_num, self.dims)
+
+    def extra_repr(self):
+        return f"iter_num={self.iter_num}, dims={self.dims}"
+
+
 class RefKeyed(nn.Module):
     """Base of the hand-written networks: parameters are plain ``nn.Parameter``s of THIS module, registered under attribute
     names without dots, and saved / loaded under the reference model's dotted state-dict keys (``model.0.weight``,

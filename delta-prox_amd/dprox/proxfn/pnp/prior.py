@@ -9,19 +9,21 @@ import torch.nn as nn
 from ... import _ops as ops
 from ...utils import safe_sqrt
 from ..core import ProxFn
-from .denoisers import Augment, DRUNetDenoiser, FFDNetColorDenoiser, FFDNetDenoiser, IRCNNDenoiser, UNetDenoiser
+from .denoisers import Augment, DRUNetDenoiser, FFDNetColorDenoiser, FFDNetDenoiser, IRCNNDenoiser, TVDenoiser, UNetDenoiser
 
 CACHE_DIR = os.path.join(os.path.expanduser("~"), ".cache", "dprox")
 
 
 def get_denoiser(type):
     """pretrained weights are read from the reference's cache layout (~/.cache/dprox/pnp_denoisers/*.pth);
-    nothing is downloaded."""
+    nothing is downloaded.  "tv" / "tv3d" (TVDenoiser(5, False) / TVDenoiser(5, True)) have no weights and need no file."""
+    if type in ("tv", "tv3d"):
+        return TVDenoiser(5, type == "tv3d")
     table = {"ffdnet": ("ffdnet_gray.pth", FFDNetDenoiser), "ffdnet_color": ("ffdnet_color.pth", FFDNetColorDenoiser),
              "drunet": ("drunet_gray.pth", lambda p: DRUNetDenoiser(1, p)), "drunet_color": ("drunet_color.pth", lambda p: DRUNetDenoiser(3, p)),
              "ircnn": ("ircnn_gray.pth", lambda p: IRCNNDenoiser(1, p)), "unet": ("unet-nm.pt", UNetDenoiser)}
     if type not in table:
-        raise ValueError(f"denoiser {type!r} is not built for the MI355X backend (have {sorted(table)}); "
+        raise ValueError(f"denoiser {type!r} is not built for the MI355X backend (have {sorted(table) + ['tv', 'tv3d']}); "
                          "pass a Denoiser instance instead")
     fname, cls = table[type]
     path = os.path.join(CACHE_DIR, "pnp_denoisers", fname)

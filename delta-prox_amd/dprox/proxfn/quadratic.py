@@ -229,6 +229,7 @@ class least_squares(ProxFn):
         self.linear_solve_config = linear_solve_config
         self._diag_cache = None
         self._ktb_cache = None
+        self._fk_cache = None
         self.cg_iters = []
 
     def _prox(self, v, lam):
@@ -253,10 +254,39 @@ class least_squares(ProxFn):
             self._ktb_cache = (key, ktb)
         return self._ktb_cache[1]
 
-    def rhs(self, b, rho, v=None):
+    def _data_spectrum(self, ref, b, rho, v):
+        """F(sum_Omega K^T offset) from float64 transforms (ops.data_spectrum) for the Fourier x-update, cached while the offsets and the
+        operator tables are unchanged -- or None: a data term other than sum_squares over x | conv(x) minus constants, nothing else on
+        the right-hand side, or something to differentiate (the op-by-op right-hand side then stands)"""
+        from ..algo import fused                       # (at call time: fused imports this package)
+        if self.quad_rhs() is None or (v is None and not len(self.other_fns)) or not all(fused._omega_ok(fn) for fn in self.quad_fns):
+            return None
+        offs = [fn.offset for fn in self.quad_fns]
+        convs = [fused._omega_conv(fn) for fn in self.quad_fns]
+        if torch.is_grad_enabled():
+            seen = list(b) + [v, rho] + offs + [getattr(cv, "psf", None) for cv in convs]
+            if any(isinstance(t, torch.Tensor) and t.requires_grad for t in seen):
+                return None
+        key = (tuple(ref.shape), str(ref.device)) + tuple(fn._offset_key() for fn in self.quad_fns) + \
+            tuple(fn.linop.tables_version() for fn in self.quad_fns)
+        hit = self._fk_cache
+        if hit is not None and hit[0] == key:
+            return hit[1]
+        FK = None
+        for off, cv in zip(offs, convs):
+            if off is None:
+                continue
+            off = (off.expand_as(ref) if off.shape != ref.shape else off).contiguous()
+            otf = cv._tables(ref.shape, ref.device) if cv is not None else None
+            FK = ops.data_spectrum(off, otf, conj=True, out=FK, accumulate=FK is not None)
+        self._fk_cache = (key, FK)
+        return FK
+
+    def rhs(self, b, rho, v=None, with_quad=True):
         terms = []
         ktb = self.quad_rhs()
-        if ktb is not None:
+        ref = ktb
+        if ktb is not None and with_quad:
             terms.append((1.0, ktb))
         for i, fn in enumerate(self.other_fns):
             kt = fn.dag.adjoint(b[i])
@@ -264,7 +294,7 @@ class least_squares(ProxFn):
                 terms.append((rho, kt))
         if v is not None:
             terms.append((rho, v))
-        ref = terms[0][1]
+        ref = terms[0][1] if ref is None else ref
         terms = [(c, t if t.shape == ref.shape else t.expand_as(ref).contiguous()) for c, t in terms]
         return ops.lincomb(terms)
 
@@ -293,7 +323,14 @@ class least_squares(ProxFn):
         return self.solve_cg(b, rho, v, self.linear_solve_config)
 
     def solve_direct(self, b, rho, v=None, eps=1e-7):
-        Ktb = self.rhs(b, rho, v)
+        # The constant part of the right-hand side enters the Fourier division as its float64 spectrum, as on the fused plan (DESIGN
+        # section 4): formed by fp32 transforms, its round-off is amplified by 1 / (|OTF|^2 + rho) -- 3e-6 of the iterate at rho = 0.06.
+        FK, ktb = None, self.quad_rhs()
+        if self.freq_diagonalizable and ktb is not None:
+            (t0, _), (t1, _) = self.diag_tables(ktb.shape, ktb.device, True)
+            if t0 is not None or t1 is not None:
+                FK = self._data_spectrum(ktb, b, rho, v)
+        Ktb = self.rhs(b, rho, v, with_quad=FK is None)
         B = Ktb.shape[0]
         (t0, c0), (t1, c1) = self.diag_tables(Ktb.shape, Ktb.device, self.freq_diagonalizable)
         if v is not None:
@@ -305,7 +342,7 @@ class least_squares(ProxFn):
             # only by eps/(diag+eps) ~ 1e-8 at pixel 0)
             return ops.lincomb([(1.0 / (c0 + rho_v * c1 + eps), Ktb)])
         if self.freq_diagonalizable:
-            return ops.fourier_solve(Ktb, t0, t1, c0, c1, rho_v, eps)
+            return ops.fourier_solve(Ktb, t0, t1, c0, c1, rho_v, eps, spec_add=FK)
         # user-supplied spatial diagonals (plugin path)
         d = (t0[1] if t0 is not None else 0.0) + c0 + rho_v.view(B, 1, 1, 1) * ((t1[1] if t1 is not None else 0.0) + c1)
         return (Ktb / (d + eps)).float()

@@ -107,6 +107,8 @@ int dpx_timing_report(char* buf, size_t cap);
  *   iter_band_min_rows   shortest band (rows) the streaming row kernel of the two-kernel iteration may     DPX_ITER_BAND_MIN_ROWS
  *                        use when few planes must fill the chip (0 = the library's rule: 4 rows, 2 for launches
  *                        of fewer than 8 planes of 1024-wide rows; bit-identical across band counts)
+ *   tv_steps             dpx_tv_denoise: at most this many TV steps per launch on one LDS tile (0 = the       DPX_TV_STEPS
+ *                        plan's choice, dpx_tv_plan; 1 = the one-step form); bit-identical for every value
  */
 int dpx_tune_count(void);
 const char* dpx_tune_name(int i);                       /* NULL beyond dpx_tune_count() */
@@ -759,6 +761,25 @@ int dpx_minres_beta(const void* zring, const void* qc, double eps, void* state, 
                     dpx_stream_t stream);
 int dpx_minres_update(void* zring, const void* q, void* qc, void* search, void* solution, void* state, int S, int G, long N, int K,
                       int is_f64, void* ws, dpx_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------ */
+/* anisotropic TV denoiser (TVDenoiser prior)                                                  */
+/* ------------------------------------------------------------------------------------------ */
+/* TV_denoising / TV_denoising3d -- proxfn/pnp/denoisers/models/TV_denoising.py:4-34 behind TVDenoiser.denoise (wrapper.py:8-22):
+ * `iters` projected dual-ascent steps on a contiguous fp32 volume y[N][D0][D1][D2] (the NCHW tensor as it stands),
+ *   x^t = (1/k) sum_{a in A} (y - D_a^T z_a^{t-1}),   z_a^t = clip(z_a^{t-1} + (1/5) D_a x^t, -lam_n / 2, +lam_n / 2),   z^0 = 0,
+ * out = x^iters (the last z update is not computed).  A = the axes whose bit is set in `axes` (bit a = axis a of [D0, D1, D2], bit 0
+ * = D0; at least one), k = |A|; an active axis of length 1 has no differences and still counts in k (an extension: the reference
+ * returns an empty tensor).  lam: [N] on the device, >= 0; lam_n = 0 returns y bit for bit.  Any N, extents >= 1 (the reference: one
+ * image); out must not be y.
+ * Up to S steps run per launch on one LDS tile with a halo of S (csrc/dpx_tv.hip); iters > S is a chain of launches over two dual
+ * buffers in `ws` (dpx_tv_ws_bytes; 0 and ws may be null when one launch suffices).  The result does not depend on S or on the tile
+ * (bit-identical; knob tv_steps caps S).  dpx_tv_plan reports what a call would do -- out6: steps per launch S, number of launches,
+ * the core tile extents t0 t1 t2, dynamic LDS bytes.                                                                          */
+size_t dpx_tv_ws_bytes(int N, int D0, int D1, int D2, int axes, int iters);
+int dpx_tv_plan(int D0, int D1, int D2, int axes, int iters, int* out6);
+int dpx_tv_denoise(const float* y, float* out, const float* lam, int N, int D0, int D1, int D2, int axes, int iters, void* ws,
+                   dpx_stream_t stream);
 
 #ifdef __cplusplus
 }
