@@ -1,8 +1,5 @@
 // Internal helpers shared by the gfx950 kernels of libdpx_hip.so (not part of the C ABI).
 #pragma once
-#ifndef DPX_COLS_PACK0
-#define DPX_COLS_PACK0 1
-#endif
 #include <hip/hip_runtime.h>
 #ifndef DPX_EMULATED
 #include <hip/hip_ext.h>
@@ -323,18 +320,21 @@ static inline int spec_cols(int W) { return (W + 1) / 2; }
 // A half spectrum / spectral table of one plane has a main part of H x Ws entries and (even W) a side
 // part of H entries for the Nyquist column l = W/2.  Generic sizes: main is row-major [H][Ws] and the
 // transform packs the Nyquist bins into the imaginary part of column 0.  Power-of-two planes: main is
-// COLUMN-TILE-MAJOR, [Ws/8][H][8] -- each 8-column tile is contiguous, so every stream of the column
-// kernel is a linear 512-byte-per-wave-instruction access -- and the Nyquist bins live in the side part.
+// COLUMN-TILE-MAJOR, [Ws/SPEC_TILE][H][SPEC_TILE] with SPEC_TILE = 16 -- each 16-column tile is contiguous, a
+// row of it is one 128-byte line, and every stream of the column kernel (8 columns per workgroup, two
+// workgroups per tile) is a linear 512-byte-per-wave-instruction access.  The side part holds the Nyquist
+// bins of the spectra that the row kernels write and read and of the operator tables; the column kernel
+// reads and writes it from the lanes of the DC column (below).
 bool pow2_path_available(int H, int W);
 #ifndef DPX_SPEC_TILE
-#define DPX_SPEC_TILE 16           // columns per spectrum tile of the power-of-two layout (4, 8 or 16): 16 = one 128-byte line per row
+#define DPX_SPEC_TILE 16           // columns per spectrum tile of the power-of-two layout (16 = one 128-byte line per row; the column kernel needs it wider than its 8 columns per workgroup)
 #endif
 constexpr int SPEC_TILE = DPX_SPEC_TILE;
 __host__ __device__ __forceinline__ size_t spec_main_index(int tiled, int H, int Ws, int k, int l) {
   return tiled ? ((size_t)(l / SPEC_TILE) * H + k) * SPEC_TILE + (l % SPEC_TILE) : (size_t)k * Ws + l;
 }
 // table = all planes' main parts [C][H*Ws] followed by all side parts [C][H]
-// Power-of-two planes, DPX_COLS_PACK0 = 1: the column kernel carries a plane's Nyquist column through its transforms as the
+// Power-of-two planes: the column kernel carries a plane's Nyquist column through its transforms as the
 // imaginary part of the DC column (dpx_fft_pow2.hip); the iteration-invariant data spectrum (dpx_data_spectrum) is stored that
 // way already -- column 0 of its main part holds A + iB, its side part is unused.  Spectra handed between the row and column
 // kernels and the tables keep the side array.

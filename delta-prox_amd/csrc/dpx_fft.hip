@@ -1097,17 +1097,7 @@ __global__ void __launch_bounds__(512) k_cols_fwd_f64(const double2* __restrict_
         const double tr = t.x, ti = conj_otf ? -(double)t.y : (double)t.y;
         n = make_double2(n.x * tr - n.y * ti, n.x * ti + n.y * tr);
       }
-      if (side_layout && !DPX_COLS_PACK0) {              // Nyquist column -> side array [P][H]
-        float2* sd = out + (size_t)P * H * Ws + (size_t)p * H + k;
-        if (accumulate) {
-          const float2 old = *sd;
-          *sd = make_float2((float)((double)old.x + n.x), (float)((double)old.y + n.y));
-        } else {
-          *sd = make_float2((float)n.x, (float)n.y);
-        }
-      } else {
-        v = make_double2(v.x - n.y, v.y + n.x);        // packed: A + i B (power-of-two planes too, see dpx_common.h)
-      }
+      v = make_double2(v.x - n.y, v.y + n.x);          // packed: A + i B (power-of-two planes too, see dpx_common.h)
     }
     float2* dst = o + spec_main_index(side_layout, H, Ws, k, l);
     if (accumulate) {

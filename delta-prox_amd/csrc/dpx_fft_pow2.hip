@@ -1,13 +1,14 @@
-// Power-of-two planes (H in {256,512,1024}, W in {256,...,2048}): the rFFT2 -> operator -> irFFT2 pipeline on
-// the register-radix transform of dpx_fft_reg.h.
+// Power-of-two planes (H and W in {256, 384, 512, 768, 1024, 1536, 2048}: 2^k and 3 * 2^k, pow2_path_available): the
+// rFFT2 -> operator -> irFFT2 pipeline on the register-radix transform of dpx_fft_reg.h.
 //
 //   k_rows_r2c_p2 : one wave (or part of one) per image row: row read as (x[2n], x[2n+1]) complex pairs with
 //                   coalesced 8-byte loads, length-W/2 transform in registers, real-input untangling with
 //                   in-wave shuffles, half spectrum written with coalesced stores; the (real) Nyquist bins go
-//                   to a small side array [P][H] so that every column of the main array is an ordinary
-//                   complex column (no packed DC/Nyquist special case in the column kernel).
+//                   to a small side array [P][H], so the row kernels have no packed DC/Nyquist special case.
 //   k_cols_p2     : a tile of COLS adjacent spectrum columns of one plane per workgroup: forward column
-//                   transform, per-frequency operator on registers, inverse column transform, in place.
+//                   transform, per-frequency operator on registers, inverse column transform.  The workgroup
+//                   with a plane's DC column carries the plane's Nyquist column (side array) through both
+//                   transforms as that column's imaginary part: the packed column.
 //   k_rows_c2r_p2 : inverse of the first.
 // Every element crosses HBM once per kernel (8 B/element algorithmic traffic each) and LDS twice per 1-D
 // transform.
@@ -278,12 +279,7 @@ __global__ void __launch_bounds__(256) k_seed_rows(SeedTerms S_, const float* __
   }
 }
 
-#ifndef DPX_PGD_LD_NT
-#define DPX_PGD_LD_NT 0
-#endif
-#ifndef DPX_PGD_ST
-#define DPX_PGD_ST 0
-#endif
+constexpr int PGD_LD_NT = 0, PGD_ST = 0;   // cache policy of k_pgd_rows' spectrum load / store (dpx_common.h)
 __device__ __forceinline__ float pgd_prox(int kind, float d, float lam) {     // (dpx_elementwise.hip::prox_eval, closed forms only)
   if (kind == DPX_PROX_NORM1) {
     const float m = fmaxf(fabsf(d) - lam, 0.f);
@@ -313,7 +309,7 @@ __global__ void __launch_bounds__(256) k_pgd_rows(const float2* __restrict__ spe
   const float2* side_in = spec_in + (size_t)nrows * M;
   float2 X[V], v[V], xo[V], kb[V];
 #pragma unroll
-  for (int m = 0; m < V; ++m) X[m] = ld_stream<DPX_PGD_LD_NT>(spec_in + toff + RM::koff(m, H));
+  for (int m = 0; m < V; ++m) X[m] = ld_stream<PGD_LD_NT>(spec_in + toff + RM::koff(m, H));
   const float xn0 = side_in[rr].x;
   // the iterate and K^T b are requested with the spectrum: ONE memory round trip in front of the transform
   float2* xr = (float2*)(x + (size_t)rr * (2 * M));
@@ -341,7 +337,7 @@ __global__ void __launch_bounds__(256) k_pgd_rows(const float2* __restrict__ spe
   if (live && t == 0) side_out[row] = make_float2(nyq, 0.f);
   if (live) {
 #pragma unroll
-    for (int m = 0; m < V; ++m) st_stream<DPX_PGD_ST>(spec_out + toff + RM::koff(m, H), X[m]);
+    for (int m = 0; m < V; ++m) st_stream<PGD_ST>(spec_out + toff + RM::koff(m, H), X[m]);
   }
 }
 
@@ -365,37 +361,21 @@ __device__ __forceinline__ float2 spec_op_p2(float2 z, const SpecArgs& A, unsign
 // ---------------------------------------------------------------------------------------------
 // columns
 // ---------------------------------------------------------------------------------------------
-// DBG (tuning experiments only, default 0): bit0 = skip both transforms, bit1 = skip the operator's table loads
-#ifndef DPX_COLS_LD_NT
-#define DPX_COLS_LD_NT 0
-#endif
-#ifndef DPX_COLS_ADD_NT
-#define DPX_COLS_ADD_NT 1       // the data spectrum is re-read once per iteration, ~1 GB of other traffic later: stream it (see dpx_iter.hip)
-#endif
-#ifndef DPX_COLS_ST
-#define DPX_COLS_ST 1           // write-through, as for the row kernel's spectrum
-#endif
-#ifndef DPX_COLS_TBL_NT
-#define DPX_COLS_TBL_NT 0
-#endif
-#ifndef DPX_COLS_TW_GLOBAL
-#define DPX_COLS_TW_GLOBAL 1
-#endif
-constexpr int COLS_LD_NT = DPX_COLS_LD_NT, COLS_ADD_NT = DPX_COLS_ADD_NT, COLS_ST = DPX_COLS_ST;   // cache policy (dpx_common.h)
-#ifndef DPX_COLS_BATCH_INNER
-#define DPX_COLS_BATCH_INNER 1
-#endif
-#ifndef DPX_COLS_PERSIST
-#define DPX_COLS_PERSIST 0       // > 0: persistent workgroups, that many per CU (tuning experiment)
-#endif
+// cache policies (dpx_common.h) of the tile load, the data-spectrum load, the tile store and the operator's table stage
+constexpr int COLS_LD_NT = 0;
+constexpr int COLS_ADD_NT = 1;      // the data spectrum is re-read once per iteration, ~1 GB of other traffic later: stream it (see dpx_iter.hip)
+constexpr int COLS_ST = 1;          // write-through, as for the row kernel's spectrum
+constexpr int COLS_TBL_NT = 0;
+constexpr int COLS_WG = 8;          // columns per workgroup of the column kernel: half a spectrum tile (H = 2048: 4, cols_dispatch)
+// waves per SIMD the register budget of k_cols_p2 is sized for (H = 768: 61 KB of LDS -> 2 workgroups of 4 waves per CU)
+constexpr int cols_waves_per_simd(int H, int T, int COLS) { return H % 3 == 0 ? 2 : T * COLS >= 512 ? 4 : 3; }
 // The Nyquist column of a plane (side array [P][H]) rides through the two transforms as the imaginary part of the plane's DC
 // column: both are spectra of real sequences, so z = dc + i ny is ONE complex column, separated by Hermitian symmetry around
 // the per-frequency operator (a = (Z[k] + conj Z[N-k]) / 2, i b = (Z[k] - conj Z[N-k]) / 2), as the generic path does
 // (dpx_fft.hip).  The HBM layout does not change: the lanes of the DC column read and write the side array themselves.
 // With separate workgroups for the Nyquist columns the launch had 3 x 512 + 3 workgroups at 8x3x1024^2 for 512 resident
 // ones, and the three extra ran alone in a fourth round: 75.7 -> 68.9 us without them.
-// The workgroup's work; PACK = its column c == 0 is the plane's packed (DC, Nyquist) column.  Two instantiations per kernel so that
-// the packed variant's extra live values (and spills) stay out of the register allocation of the other 63 workgroups in 64.
+
 // Tuning aid (variant builds with -DDPX_PAR_TRACE only, tools/par_trace.py): 100 MHz real-time stamps of every wave of the first 256 workgroups
 #ifdef DPX_PAR_TRACE
 __device__ unsigned long long dpx_cols_trace_buf[256 * 16 * 10];
@@ -409,7 +389,10 @@ extern "C" int dpx_dbg_cols_trace(unsigned long long* host, int n) {
 #else
 #define DPX_CSTAMP(i) ((void)0)
 #endif
-template <int H, int T, int COLS, int OP, int DBG, bool PACK>
+
+// The workgroup's work; PACK = its column c == 0 is the plane's packed (DC, Nyquist) column.  Two instantiations per kernel so that
+// the packed variant's extra live values (and spills) stay out of the register allocation of the other 63 workgroups in 64.
+template <int H, int T, int COLS, int OP, bool PACK>
 __device__ __forceinline__ void cols_body(const float2* __restrict__ spec_in, float2* __restrict__ spec_out, const SpecArgs& A, int C, int Ws, int P,
                                           const float2* __restrict__ twH, int bid, int nmain, bool is_side, int p, int j, unsigned sub_off) {
   constexpr int V = H / T;
@@ -427,8 +410,7 @@ __device__ __forceinline__ void cols_body(const float2* __restrict__ spec_in, fl
   // uniform (scalar) bases + 32-bit per-thread element offsets: one address VGPR per access
   size_t ubase;                                       // element offset of the tile's plane / of the side array
   unsigned off0, off0k, step, toff0, tbase;           // data offset of image row t TMUL / of frequency row t, offset of one row, table offset of row t, table base
-  constexpr bool pack0 = PACK;
-  if (!is_side) {
+  if (!is_side) {                                     // (always: see is_side in k_cols_p2)
     ubase = (size_t)p * H * Ws + (size_t)j * H * SPEC_TILE;   // tile-major main part: element (row r, col c) of a tile at r*TILE + c
     off0k = (unsigned)((c / SPEC_TILE) * H * SPEC_TILE + t * SPEC_TILE + (c % SPEC_TILE)) + sub_off;
     off0 = off0k + (unsigned)((TMUL - 1) * t * SPEC_TILE);
@@ -451,32 +433,12 @@ __device__ __forceinline__ void cols_body(const float2* __restrict__ spec_in, fl
   float2* lds = smem_p2 + c * S;
   // the H column twiddles, shared by the workgroup: an LDS copy -- except for H = 2048, where the copy's 16 KB would leave room for
   // one 4-column workgroup per CU instead of two (81920 B each without it): there they are read from the table (L1 / L2 resident)
-  constexpr bool TWG = DPX_COLS_TW_GLOBAL && (H >= 2048);
+  constexpr bool TWG = (H >= 2048);
   const float2* twl = TWG ? twH : smem_p2 + COLS * S;
   float2 v[V];
-  // Input tile.  DMA_IN: by LDS-DMA, 16 bytes per lane (a wave instruction moves 16 rows x 64 bytes = 1 KB instead of 8 x 64), into
-  // the exchange buffer, each wave fetching exactly the rows its own lanes hold (piece j = rows t + T (2j + half), the table stage's
-  // lane map: value m of this lane lands at float2 index m * 64 + lane of the wave's image).  Piece j of wave w lands in column region j
-  // at slots [136 w, 136 w + 128) -- precisely the slots (17 t + m, t = 8 w .. 8 w + 7) this wave overwrites itself in the first pass,
-  // after it has read them (one wave's LDS operations execute in order): no other wave's stage is touched, no barrier is needed.
-  // Measured at 8x3x1024^2 (round 4, alternating runs on one box): k_cols_p2 72.3 us with it, 69.6 - 70.7 us without -- half the load
-  // instructions and no address arithmetic, but the tile crosses the LDS once more and the first pass waits for a full vmcnt(0): OFF.
-#ifndef DPX_COLS_DMA_IN
-#define DPX_COLS_DMA_IN 0
-#endif
-  constexpr bool DMA_IN = DPX_COLS_DMA_IN && DPX_COLS_PACK0 && !R3 && COLS == 8 && V == 16 && SPEC_TILE == 16 && !DBG;
-  if constexpr (DMA_IN) {
-    constexpr int RPW = 64 / COLS, LPR = COLS / 2;
-    const int lane_ = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int half = lane_ >> 5, li = lane_ & 31;
-    const float2* src = (const float2*)pin + (unsigned)((RPW * wv + li / LPR + T * half) * SPEC_TILE + (li % LPR) * 2) + sub_off;
-    float2* stg = smem_p2 + wv * (V * RPW + RPW);        // 17 * 8 slots per wave and column region
+  // Input tile, 8 bytes per lane.  (By LDS-DMA into the exchange buffer, 16 bytes per lane: 72.3 us against 69.6 - 70.7 at 8x3x1024^2)
 #pragma unroll
-    for (int j = 0; j < V / 2; ++j) dpx_glds16<COLS_LD_NT>(src + j * 2 * T * SPEC_TILE, stg + j * S);
-  } else {
-#pragma unroll
-    for (int m = 0; m < V; ++m) v[m] = ld_stream<COLS_LD_NT>((const float2*)(pin + (off0 + step * hrow(m)) * 8u));
-  }
+  for (int m = 0; m < V; ++m) v[m] = ld_stream<COLS_LD_NT>((const float2*)(pin + (off0 + step * hrow(m)) * 8u));
   const bool dc_lane = PACK && c == 0;               // the lanes carrying the packed (DC, Nyquist) column
   float sidev[PACK ? V : 1];
   if (dc_lane) {                                      // (row spectra: both columns are real on entry)
@@ -484,15 +446,12 @@ __device__ __forceinline__ void cols_body(const float2* __restrict__ spec_in, fl
 #pragma unroll
     for (int m = 0; m < V; ++m) sidev[PACK ? m : 0] = sidef[2 * hrow(m)];
   }
-  // DPX_COLS_PACK_EARLY: the packed column's Nyquist denominators are requested with the tile (V floats per lane of the packed
+  // Solve: the packed column's Nyquist denominators are requested with the tile (V floats per lane of the packed
   // column's instantiation, alive through the forward transform) instead of behind the operator, where their memory round trip
   // made the launch's three packed workgroups its last to finish (1 x 3 x 1024^2: 17.0 us against 13.6 for the others)
-#ifndef DPX_COLS_PACK_EARLY
-#define DPX_COLS_PACK_EARLY 1
-#endif
-  constexpr bool PACK_EARLY = DPX_COLS_PACK_EARLY && PACK && OP == OP_SOLVE;
-  float dnb_early[PACK_EARLY ? V : 1];
-  if constexpr (PACK_EARLY) {
+  constexpr bool PACK_SOLVE = PACK && OP == OP_SOLVE;
+  float dnb_early[PACK_SOLVE ? V : 1];
+  if constexpr (PACK_SOLVE) {
     if (dc_lane) {
       const float rb = A.rho ? A.rho[p / C] : 0.f;
       const float2* tsd0 = A.dd + (unsigned)C * H * Ws + (unsigned)(p % C) * H + t;
@@ -506,12 +465,6 @@ __device__ __forceinline__ void cols_body(const float2* __restrict__ spec_in, fl
   if constexpr (!TWG) {
     for (int i = tid; i < H; i += T * COLS) smem_p2[COLS * S + i] = twH[i];
   }
-  if constexpr (DMA_IN) {
-    dpx_wait_vm<0>();                                 // this wave's pieces have landed (and its twiddle / side loads returned)
-    const float2* stg = smem_p2 + __builtin_amdgcn_readfirstlane(tid >> 6) * (V * (64 / COLS) + 64 / COLS) + (tid & 63);
-#pragma unroll
-    for (int m = 0; m < V; ++m) v[m] = stg[(m >> 1) * S + (m & 1) * 64];
-  }
   if (dc_lane) {
 #pragma unroll
     for (int m = 0; m < V; ++m) v[m].y = sidev[PACK ? m : 0];
@@ -524,26 +477,20 @@ __device__ __forceinline__ void cols_body(const float2* __restrict__ spec_in, fl
   // transform's exchange buffer while it is idle -- between the forward transform's last LDS read and the inverse
   // transform's first write -- so that they cost no registers; each wave fetches exactly the rows its own lanes use
   // (lane-linear image: float2 index m*64 + lane of the wave's 8 KB), so its own vmcnt wait is all the
-  // synchronisation the data needs.  The data-spectrum values (HBM) are requested in one batch right behind them:
-  // ONE memory round trip between the two transforms.
-#ifndef DPX_COLS_MUL_DMA
-#define DPX_COLS_MUL_DMA 1         // the multiply operators stage their OTF values the same way (direct loads at the operator: 81.5 us at 8x3x1024^2)
-#endif
-  constexpr bool DMA_TABLE = (OP == OP_SOLVE || DPX_COLS_MUL_DMA) && (COLS == 8 || COLS == 4) && (V % 2 == 0) && !(DBG & 2);
-#ifndef DPX_COLS_EARLY_ADD
-#define DPX_COLS_EARLY_ADD 1       // with the spectra served from the Infinity Cache the data spectrum is the HBM stream: start it one pass earlier (78.8 -> 76.0 us)
-#endif
-  constexpr bool EARLY_ADD = DPX_COLS_EARLY_ADD;        // request the data spectrum before the last pass's arithmetic
-  constexpr int NAV = (OP == OP_SOLVE || DPX_COLS_PACK0) ? V : 1;
-  float2 av[NAV];                                     // data spectrum (SOLVE); MUL: the packed column's correction
+  // synchronisation the data needs.  The multiply operators stage their OTF values the same way (direct loads at the
+  // operator: 81.5 us at 8x3x1024^2).  The data-spectrum values (HBM) are requested in one batch right behind them,
+  // before the last pass's arithmetic: ONE memory round trip between the two transforms, and with the spectra served
+  // from the Infinity Cache the data spectrum is the HBM stream, so it starts one pass earlier (78.8 -> 76.0 us).
+  static_assert((COLS == 8 || COLS == 4) && V % 2 == 0, "the table stage's lane map: 16-byte pieces of 8- or 4-column rows, two rows of a lane per piece");
+  float2 av[V];                                       // data spectrum (SOLVE); MUL: the packed column's correction
 #pragma unroll
-  for (int m = 0; m < NAV; ++m) av[m] = make_float2(0.f, 0.f);
+  for (int m = 0; m < V; ++m) av[m] = make_float2(0.f, 0.f);
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   float2* tstage = smem_p2 + wave * (64 * V);
   auto fetch_table = [&]() {
     DPX_CSTAMP(8);
-    if (DMA_TABLE && !is_side) {
+    if (!is_side) {
       DPX_LDS_BARRIER();                                // every wave has read its last-pass inputs
       // piece j: rows T*(2j + half) + RPW*wave + li/LPR (half = lane / 32, li = lane % 32), columns 2*(li % LPR), +1
       constexpr int RPW = 64 / COLS, LPR = COLS / 2;      // rows per wave and 16-byte lanes per row
@@ -553,14 +500,14 @@ __device__ __forceinline__ void cols_body(const float2* __restrict__ spec_in, fl
       const float2* src = (OP == OP_SOLVE ? A.dd : A.otf) + tbase + (unsigned)((RPW * wave + li / LPR) * SPEC_TILE + (li % LPR) * 2) + sub_off;
       if constexpr (R3) {                                 // (pieces 2j, 2j+1 are not a constant distance apart)
 #pragma unroll
-        for (int j = 0; j < V / 2; ++j) dpx_glds16<DPX_COLS_TBL_NT>(src + (half ? krow(2 * j + 1) : krow(2 * j)) * SPEC_TILE, tstage + j * 128);
+        for (int j = 0; j < V / 2; ++j) dpx_glds16<COLS_TBL_NT>(src + (half ? krow(2 * j + 1) : krow(2 * j)) * SPEC_TILE, tstage + j * 128);
       } else {
         src += T * half * SPEC_TILE;
 #pragma unroll
-        for (int j = 0; j < V / 2; ++j) dpx_glds16<DPX_COLS_TBL_NT>(src + j * 2 * T * SPEC_TILE, tstage + j * 128);
+        for (int j = 0; j < V / 2; ++j) dpx_glds16<COLS_TBL_NT>(src + j * 2 * T * SPEC_TILE, tstage + j * 128);
       }
     }
-    if constexpr (OP == OP_SOLVE && EARLY_ADD) {
+    if constexpr (OP == OP_SOLVE) {
       unsigned offa = off0k;
       DPX_OPAQUE(offa);
       if (add) {
@@ -574,15 +521,10 @@ __device__ __forceinline__ void cols_body(const float2* __restrict__ spec_in, fl
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   DPX_CSTAMP(1);
 #endif
-  if (!(DBG & 1)) {
-    if constexpr (R3) fft_reg_x3<H / 3, T, -1>(v, lds, t, twl, 1, BlockSync(), fetch_table);
-    else fft_reg<H, T, -1>(v, lds, t, twl, 1, BlockSync(), fetch_table);
-  }
+  if constexpr (R3) fft_reg_x3<H / 3, T, -1>(v, lds, t, twl, 1, BlockSync(), fetch_table);
+  else fft_reg<H, T, -1>(v, lds, t, twl, 1, BlockSync(), fetch_table);
   DPX_CSTAMP(2);
   __builtin_amdgcn_sched_barrier(0);
-#ifdef DPX_COLS_PRIO
-  __builtin_amdgcn_s_setprio(DPX_COLS_PRIO);          // experiment: workgroups past their forward transform go first
-#endif
   // Packed column (its workgroup only, PACK): Z = A + iB is split into A = (Z + Zc)/2 and iB = (Z - Zc)/2, Zc[k] = conj Z[N-k], so
   // that the operator's factors of the DC column (fA) and of the Nyquist column (fB) reach their own parts:
   //     op(Z) = fA (A + eps) + fB (iB + i eps) = fA (Z + eps) + (fB - fA) iB + i fB eps.
@@ -618,12 +560,8 @@ __device__ __forceinline__ void cols_body(const float2* __restrict__ spec_in, fl
   if constexpr (OP == OP_SOLVE) {
     unsigned offa = off0k;
     DPX_OPAQUE(offa);
-    if (!EARLY_ADD && add) {
-#pragma unroll
-      for (int m = 0; m < V; ++m) av[m] = ld_stream<COLS_ADD_NT>((const float2*)(add + (offa + step * krow(m)) * 8u));
-    }
-    if (DMA_TABLE && !is_side) {
-      if (add) dpx_wait_vm<V>();                        // the V data-spectrum loads above may stay in flight
+    if (!is_side) {
+      if (add) dpx_wait_vm<V>();                        // the V data-spectrum loads of fetch_table may stay in flight
       else dpx_wait_vm<0>();
 #pragma unroll
       for (int m = 0; m < V; ++m) {
@@ -637,22 +575,21 @@ __device__ __forceinline__ void cols_body(const float2* __restrict__ spec_in, fl
 #pragma unroll
       for (int m = 0; m < V; ++m) {
         const float2 z = cadd(v[m], av[m]);
-        if (DBG & 2) v[m] = cscale(z, A.scale);
-        else v[m] = spec_op_p2<OP>(z, A, tbase + toff0 + step * krow(m), rho_b);
+        v[m] = spec_op_p2<OP>(z, A, tbase + toff0 + step * krow(m), rho_b);
         if (V > 8 && (m & 3) == 3) __builtin_amdgcn_sched_barrier(0);
       }
     }
   } else {
 #pragma unroll
     for (int m = 0; m < V; ++m) {
-      if (DMA_TABLE && !is_side) {
+      if (!is_side) {
         if (m == 0) dpx_wait_vm<0>();
         const float2 o = tstage[m * 64 + lane];
         v[m] = cscale(OP == OP_MULCONJ ? cmulc(v[m], o) : cmul(v[m], o), A.scale);
       } else {
         v[m] = spec_op_p2<OP>(v[m], A, tbase + toff0 + step * krow(m), rho_b);
       }
-      if (DPX_COLS_PACK0) v[m] = cadd(v[m], av[m]);     // (zero except in the packed column)
+      v[m] = cadd(v[m], av[m]);                         // (zero except in the packed column)
       if (V > 8 && (m & 3) == 3) __builtin_amdgcn_sched_barrier(0);
     }
   }
@@ -662,23 +599,17 @@ __device__ __forceinline__ void cols_body(const float2* __restrict__ spec_in, fl
     asm volatile("" ::: "memory");                    // (keeps the loads below behind the operator: hoisted across it they spill)
     const float iscale = 1.0f / A.scale;
     float dnb[V], g[V];                               // the Nyquist column's and the DC column's denominators
-    if (!DMA_TABLE) DPX_LDS_BARRIER();                  // (with the table stage, its barrier already separates the last-pass reads from these writes)
+    // (the table stage's barrier already separates the last-pass reads from the exchange buffer's writes below)
     if (dc_lane) {
+      // (the copy inside this branch and the fence on ts, which feeds nothing, remain of the denominators' load at this place:
+      //  without either of them the packed solve kernels' registers are allocated differently)
       int ts = t;
       DPX_OPAQUE(ts);
-      const float2* tsd = A.dd + (unsigned)C * H * Ws + (unsigned)(p % C) * H + ts;
+#pragma unroll
+      for (int m = 0; m < V; ++m) dnb[m] = dnb_early[m];
 #pragma unroll
       for (int m = 0; m < V; ++m) {
-        if constexpr (PACK_EARLY) {
-          dnb[m] = dnb_early[m];
-        } else {
-          const float2 db = tsd[krow(m)];
-          dnb[m] = fmaf(rho_b, db.y, db.x) + A.eps;
-        }
-      }
-#pragma unroll
-      for (int m = 0; m < V; ++m) {
-        const float2 da = (DMA_TABLE && !(DBG & 2)) ? tstage[m * 64 + lane] : A.dd[tbase + toff0 + step * krow(m)];
+        const float2 da = tstage[m * 64 + lane];
         g[m] = fmaf(rho_b, da.y, da.x) + A.eps;
         xslot(t + krow(m))[0] = make_float2(fmaf(v[m].x, g[m] * iscale, -A.eps_num), v[m].y * (g[m] * iscale));
       }
@@ -699,10 +630,8 @@ __device__ __forceinline__ void cols_body(const float2* __restrict__ spec_in, fl
   DPX_CSTAMP(3);
   DPX_LDS_BARRIER();
   DPX_CSTAMP(4);
-  if (!(DBG & 1)) {
-    if constexpr (R3) fft_reg_x3<H / 3, T, +1>(v, lds, t, twl, 1, BlockSync());
-    else fft_reg<H, T, +1>(v, lds, t, twl, 1, BlockSync());
-  }
+  if constexpr (R3) fft_reg_x3<H / 3, T, +1>(v, lds, t, twl, 1, BlockSync());
+  else fft_reg<H, T, +1>(v, lds, t, twl, 1, BlockSync());
   DPX_CSTAMP(5);
   unsigned off1 = off0;
   DPX_OPAQUE(off1);       // do not keep the load offsets alive for the stores
@@ -723,67 +652,53 @@ __device__ __forceinline__ void cols_body(const float2* __restrict__ spec_in, fl
 }
 
 
-template <int H, int T, int COLS, int OP, int DBG = 0>
-#ifndef DPX_COLS_WPE
-#define DPX_COLS_WPE ((H % 3 == 0 || (H >= 2048 && !DPX_COLS_TW_GLOBAL)) ? 2 : (T * COLS) >= 512 ? 4 : 3)     // waves per SIMD the register budget is sized for (H = 768: 61 KB of LDS -> 2 workgroups of 4 waves per CU)
-#endif
-__global__ void __launch_bounds__(T* COLS, DPX_COLS_WPE) k_cols_p2(const float2* __restrict__ spec_in, float2* __restrict__ spec_out, SpecArgs A,
+// (total_blocks, the launch's workgroup count, is not read: it stays so that the kernel's argument block, and with it the
+//  compiled kernel, is the one that was measured)
+template <int H, int T, int COLS, int OP>
+__global__ void __launch_bounds__(T* COLS, cols_waves_per_simd(H, T, COLS)) k_cols_p2(const float2* __restrict__ spec_in, float2* __restrict__ spec_out, SpecArgs A,
                                                       int C, int Ws, int P, const float2* __restrict__ twH, int total_blocks) {
+  static_assert(COLS < SPEC_TILE, "several workgroups per spectrum tile");
   const int tiles = Ws / COLS, nmain = P * tiles;
-#if DPX_COLS_PERSIST
-  // persistent form: the launch has at most DPX_COLS_PERSIST workgroups per CU's worth of blocks; each walks block ids bid, bid + grid, ...
-  // (same XCD: the grid is a multiple of 8) -- the next tile's loads are issued while this tile's stores drain
-  for (int bid = blockIdx.x; bid < total_blocks; bid += gridDim.x) {
-#else
   const int bid = blockIdx.x;
-#endif
-  // main tiles: COLS adjacent columns of plane p.  side tiles (DPX_COLS_PACK0 = 0 only): the Nyquist columns of COLS consecutive planes.
+  // main tiles: COLS adjacent columns of plane p.  side tiles: the Nyquist columns of COLS consecutive planes, from before the packed
+  // column.  The launch has exactly nmain workgroups, so is_side is never true and the side arm of cols_body (with spec_op_p2) never
+  // runs.  It stays a run-time value all the same: folded to false, the register allocation of the solve kernels goes from 110 to 128
+  // VGPRs with 48 B (H = 1024) and 36 B (H = 2048) of scratch, and from 159 - 160 to 206 - 208 VGPRs at H = 384 / 768 / 1536.
+  // Removing the arm is a performance change, to be measured on the GPU.
   const bool is_side = bid >= nmain;                  // block-uniform
   int p = 0, j = 0;                                   // plane and first spectrum tile of this workgroup
   unsigned sub_off = 0;                               // column offset of this workgroup inside a wider spectrum tile
   if (!is_side) {
     p = bid / tiles;
-    if constexpr (COLS >= SPEC_TILE) {
-      j = (bid - p * tiles) * (COLS / SPEC_TILE);
+    // SPEC_TILE / COLS workgroups share a tile (and its 128-byte lines): they are placed 8 block ids apart so that
+    // the round-robin block -> XCD assignment puts them on the same XCD, i.e. behind the same L2
+    constexpr int SUB = SPEC_TILE / COLS;
+    const int tiles_w = Ws / SPEC_TILE, Bn = P / C;   // spectrum tiles per plane, images
+    if ((C * tiles_w) % 8 == 0) {
+      // ... and so are the Bn images' workgroups of one (channel, tile): the operator's table (denominators / OTF) is
+      // shared by the batch, and with the images innermost on one XCD its lines are fetched from HBM once instead of
+      // once per image (the streams in between would evict them from the 4 MB L2).
+      // bid = 8 * ((g * Bn + b) * SUB + sub) + xcd,  (channel, tile) = g * 8 + xcd
+      const int per = 8 * Bn * SUB, u = bid / per, r = bid - u * per, ng = (C * tiles_w) / 8;
+      const int bg = u / ng, g = u - bg * ng;
+      const int xs = r % 8, sidx = r / 8, ct = g * 8 + xs;
+      // (channel, tile) pairs in tile-major order: the workgroups holding a packed (DC, Nyquist) column -- tile 0 of every channel,
+      // a few microseconds longer than the rest -- are dispatched first instead of ending up in the launch's last round
+      const int cch = ct % C;
+      j = ct / C;
+      p = (bg * Bn + sidx / SUB) * C + cch;
+      sub_off = (unsigned)((sidx % SUB) * COLS);
     } else {
-      // SPEC_TILE / COLS workgroups share a tile (and its 128-byte lines): they are placed 8 block ids apart so that
-      // the round-robin block -> XCD assignment puts them on the same XCD, i.e. behind the same L2
-      constexpr int SUB = SPEC_TILE / COLS;
-      const int tiles_w = Ws / SPEC_TILE, Bn = P / C;   // spectrum tiles per plane, images
-      if (DPX_COLS_BATCH_INNER && (C * tiles_w) % 8 == 0) {
-        // ... and so are the Bn images' workgroups of one (channel, tile): the operator's table (denominators / OTF) is
-        // shared by the batch, and with the images innermost on one XCD its lines are fetched from HBM once instead of
-        // once per image (the streams in between would evict them from the 4 MB L2).
-        // bid = 8 * ((g * Bn + b) * SUB + sub) + xcd,  (channel, tile) = g * 8 + xcd
-        const int GB = (DPX_COLS_BATCH_INNER > 1 && Bn % DPX_COLS_BATCH_INNER == 0) ? DPX_COLS_BATCH_INNER : Bn;   // images per inner group
-        const int per = 8 * GB * SUB, u = bid / per, r = bid - u * per, ng = (C * tiles_w) / 8;
-        const int bg = u / ng, g = u - bg * ng;
-        const int xs = r % 8, sidx = r / 8, ct = g * 8 + xs;
-        // (channel, tile) pairs in tile-major order: the workgroups holding a packed (DC, Nyquist) column -- tile 0 of every channel,
-        // a few microseconds longer than the rest -- are dispatched first instead of ending up in the launch's last round
-        const int cch = DPX_COLS_PACK0 ? ct % C : ct / tiles_w;
-        j = DPX_COLS_PACK0 ? ct / C : ct - cch * tiles_w;
-        p = (bg * GB + sidx / SUB) * C + cch;
-        sub_off = (unsigned)((sidx % SUB) * COLS);
-      } else {
-        const int q = bid - p * tiles;
-        j = (q / (8 * SUB)) * 8 + (q % 8);
-        sub_off = (unsigned)(((q % (8 * SUB)) / 8) * COLS);
-      }
+      const int q = bid - p * tiles;
+      j = (q / (8 * SUB)) * 8 + (q % 8);
+      sub_off = (unsigned)(((q % (8 * SUB)) / 8) * COLS);
     }
   }
-  if (DPX_COLS_PACK0 && !is_side && j == 0 && sub_off == 0)
-    cols_body<H, T, COLS, OP, DBG, true>(spec_in, spec_out, A, C, Ws, P, twH, bid, nmain, is_side, p, j, sub_off);
+  if (!is_side && j == 0 && sub_off == 0)
+    cols_body<H, T, COLS, OP, true>(spec_in, spec_out, A, C, Ws, P, twH, bid, nmain, is_side, p, j, sub_off);
   else
-    cols_body<H, T, COLS, OP, DBG, false>(spec_in, spec_out, A, C, Ws, P, twH, bid, nmain, is_side, p, j, sub_off);
-#if DPX_COLS_PERSIST
-    __syncthreads();                                  // the inverse transform's last LDS reads / the next tile's first writes
-  }
-#endif
+    cols_body<H, T, COLS, OP, false>(spec_in, spec_out, A, C, Ws, P, twH, bid, nmain, is_side, p, j, sub_off);
 }
-
-// Tuning probe (DPX_DEBUG_COLS=4, wrong results by design): the column kernel's HBM traffic with 16-byte accesses and
-// no arithmetic -- the ceiling a wide-access version of k_cols_p2 could reach at the same occupancy.
 
 // ---------------------------------------------------------------------------------------------
 // host dispatch
@@ -811,33 +726,21 @@ static void rows_dispatch(bool fwd, int W, int H, const float* x, float2* spec, 
   if (!launched) launch_fail("k_rows_%s_p2: no instantiation for %d-wide rows", fwd ? "r2c" : "c2r", W);
 }
 
-template <int H, int T, int COLS, int OP, int DBG = 0>
+template <int H, int T, int COLS, int OP>
 static void launch_cols(const float2* spec, float2* spec_out, const SpecArgs& A, int P, int C, int Ws, const float2* twH, hipStream_t s) {
   constexpr int S0 = LdsSeq<H>::SLOTS;
   constexpr int S = S0 + ((36 - S0 % 32) % 32);
-  // + the rest of the packed column's H-bin exchange buffer (DPX_COLS_PACK0): 80 KB per workgroup at H = 1024, still two per CU
-  constexpr bool TWG = DPX_COLS_TW_GLOBAL && (H >= 2048);      // (cols_body: no LDS copy of the twiddles)
-  const size_t sh = (size_t)(COLS * S + (TWG ? 0 : H) + (DPX_COLS_PACK0 && H > COLS * (S - H) ? H - COLS * (S - H) : 0)) * sizeof(float2);
-  const int total_blocks = P * (Ws / COLS) + (DPX_COLS_PACK0 ? 0 : (P + COLS - 1) / COLS);
-  int grid = total_blocks;
-#if DPX_COLS_PERSIST
-  {
-    const int cap = 256 * DPX_COLS_PERSIST;
-    if (grid > cap) grid = cap;
-  }
-#endif
-  DPX_LAUNCH_LDS("k_cols_p2", (k_cols_p2<H, T, COLS, OP, DBG>), dim3(grid), dim3(T * COLS), sh, s, spec, spec_out, A, C, Ws, P, twH, total_blocks);
+  // + the rest of the packed column's H-bin exchange buffer: 80 KB per workgroup at H = 1024, still two per CU
+  constexpr bool TWG = (H >= 2048);      // (cols_body: no LDS copy of the twiddles)
+  const size_t sh = (size_t)(COLS * S + (TWG ? 0 : H) + (H > COLS * (S - H) ? H - COLS * (S - H) : 0)) * sizeof(float2);
+  const int total_blocks = P * (Ws / COLS);
+  DPX_LAUNCH_LDS("k_cols_p2", (k_cols_p2<H, T, COLS, OP>), dim3(total_blocks), dim3(T * COLS), sh, s, spec, spec_out, A, C, Ws, P, twH, total_blocks);
 }
-
-#ifndef DPX_COLS_WG
-#define DPX_COLS_WG (SPEC_TILE > 8 ? 8 : SPEC_TILE)
-#endif
-constexpr int COLS_WG = DPX_COLS_WG;   // columns per workgroup of the column kernel
 
 template <int OP>
 static void cols_dispatch(int H, const float2* spec, float2* spec_out, const SpecArgs& A, int P, int C, int Ws, const float2* twH, hipStream_t s) {
   // (measured and removed -- round 5: 4-column workgroups for launches of a few planes, 16.9 -> 22.8 us; the transform-free / wide-access
-  //  probe forms of this kernel behind the debug knob: DESIGN.md section 3)
+  //  probe forms of this kernel: DESIGN.md section 3)
   switch (H) {
     case 256: launch_cols<256, 32, COLS_WG, OP>(spec, spec_out, A, P, C, Ws, twH, s); break;
     case 512: launch_cols<512, 64, COLS_WG, OP>(spec, spec_out, A, P, C, Ws, twH, s); break;

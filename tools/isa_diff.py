@@ -5,7 +5,10 @@ A file that differs is compared once more function by function (labels carry the
 "same functions, other order" means the kernels are emitted in another order and nothing else differs.
 
     python tools/isa_diff.py PARENT_TREE [THIS_TREE]      # one line per file; exit status 1 unless every file is one of the two
+    --rename 'PATTERN=REPLACEMENT'   a regex substitution (split at the last '=') applied to the whole of PARENT_TREE's assembly before
+                                     comparing, for a change that renames symbols, such as one that drops a template parameter
 """
+import argparse
 import glob
 import os
 import re
@@ -40,8 +43,10 @@ def functions(lines):
     return out
 
 
-def compare(name, a_tree, b_tree):
+def compare(name, a_tree, b_tree, rename=None):
     a, b = (asm(os.path.join(t, "delta-prox_amd", "csrc", name)) for t in (a_tree, b_tree))
+    if rename:
+        a = re.sub(rename[0], rename[1], "\n".join(a)).split("\n")
     kernels = lambda ls: sorted(l.split()[1] for l in ls if l.strip().startswith(".amdhsa_kernel "))
     ka, kb = kernels(a), kernels(b)
     if a == b:
@@ -54,9 +59,14 @@ def compare(name, a_tree, b_tree):
 
 
 if __name__ == "__main__":
-    parent, this = sys.argv[1], (sys.argv[2] if len(sys.argv) > 2 else ROOT)
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("parent")
+    ap.add_argument("this", nargs="?", default=ROOT)
+    ap.add_argument("--rename", type=lambda v: v.rpartition("=")[::2])
+    args = ap.parse_args()
+    parent, this = args.parent, args.this
     names = sorted(os.path.basename(p) for p in glob.glob(os.path.join(this, "delta-prox_amd", "csrc", "*.hip")))
     with ThreadPoolExecutor(8) as ex:
-        res = list(ex.map(lambda n: compare(n, parent, this), names))
+        res = list(ex.map(lambda n: compare(n, parent, this, args.rename), names))
     print("\n".join(res))
     sys.exit(any("DIFFER" in r for r in res))
