@@ -347,10 +347,7 @@ __global__ void __launch_bounds__(64 * NW, 4) k_bwd_rows_par(const float2* __res
   }
 }
 
-#ifndef DPX_BWD_PAR_NW
-#define DPX_BWD_PAR_NW 8           // waves per workgroup (two workgroups per CU; 16: one)
-#endif
-constexpr int BWD_PAR_NW = DPX_BWD_PAR_NW;
+constexpr int BWD_PAR_NW = 8;      // waves per workgroup (two workgroups per CU; 16: one)
 
 int bwd_rows_par_own(int P, int H, int W) {
   if (!(W == 256 || W == 512 || W == 1024)) return 0;      // (so rows_wave_lanes(W) below is 16, 32 or 64)

@@ -182,9 +182,9 @@ extern "C" size_t dpx_cg_masked_fft_ws_bytes(int B, int H, int W, int mask_image
 // Spin until the device has stored `tag` at *slot (host-coherent memory, written by the finishing workgroup of a launch already in the
 // stream, together with the word next to it: one 8-byte store).  Once a millisecond (by the clock, not by a spin count) it looks at the stream:
 // a drained stream makes every store of its kernels visible whatever the platform does with device stores to pinned memory in mid-kernel, so
-// the answer is then final -- the tag, or false (also for a failed stream).  The one-minute limit guards against a store that never comes
-// although the stream drains normally -- it only runs while the stream reports work in flight AFTER the tag's own launch could have run, i.e.
-// it is restarted whenever the stream makes progress the host can see: a stream with minutes of earlier work in front of the solve is waited for.
+// the answer is then final -- the tag, or false (also for a failed stream).  The one-minute limit counts from the call and is never restarted:
+// a stream that still reports work in flight a minute later is handed to the blocking hipStreamSynchronize, so a solve queued behind minutes
+// of earlier work is still waited for, only no longer by spinning.
 static bool wait_for_tag(volatile int* slot, int tag, hipStream_t s) {
   using clock = std::chrono::steady_clock;
   auto t_query = clock::now(), t_limit = t_query;

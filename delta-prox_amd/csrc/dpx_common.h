@@ -326,10 +326,7 @@ static inline int spec_cols(int W) { return (W + 1) / 2; }
 // bins of the spectra that the row kernels write and read and of the operator tables; the column kernel
 // reads and writes it from the lanes of the DC column (below).
 bool pow2_path_available(int H, int W);
-#ifndef DPX_SPEC_TILE
-#define DPX_SPEC_TILE 16           // columns per spectrum tile of the power-of-two layout (16 = one 128-byte line per row; the column kernel needs it wider than its 8 columns per workgroup)
-#endif
-constexpr int SPEC_TILE = DPX_SPEC_TILE;
+constexpr int SPEC_TILE = 16;      // columns per spectrum tile of the power-of-two layout (16 = one 128-byte line per row; the column kernel needs it wider than its 8 columns per workgroup)
 __host__ __device__ __forceinline__ size_t spec_main_index(int tiled, int H, int Ws, int k, int l) {
   return tiled ? ((size_t)(l / SPEC_TILE) * H + k) * SPEC_TILE + (l % SPEC_TILE) : (size_t)k * Ws + l;
 }

@@ -20,12 +20,6 @@
 #include "dpx_prox_dev.h"
 #include "dpx_mma_dev.h"
 
-// Tuning probes (wrong results by design; DESIGN.md section 3 has what they measured): 1 tap-independent fragment reads,
-// 2 no split pass, 4 no DMA / waits / barriers, 8 no DMA (barriers stay), 16 DMA never waited for,
-// 32 / 64 every activation piece from one cached KB of zeros / of image data.
-#ifndef DPX_BX_DBG
-#define DPX_BX_DBG 0
-#endif
 namespace dpx {
 
 __device__ unsigned g_f16_overflow = 0u;                              // set by any split-f16 layer that met |x| > 6e4 (NaN counts)
@@ -209,7 +203,6 @@ __global__ void __launch_bounds__(TH * 32, TH == 16 ? 1 : 2) k_conv3x3_bf16(cons
     for (int k = 0; k < NPI; ++k) poff[k] = piece_off(k, tid);
   }
   auto issue_act = [&](int c) {
-    if (DPX_BX_DBG & 8) return;
     const float* cb = inb + (size_t)(2 * c) * H * W * 8;
     int tid_c = tid;
     if constexpr (!POFF_TABLE) DPX_OPAQUE(tid_c);                     // (per chunk: the offsets must not be hoisted out of the chunk loop)
@@ -219,14 +212,12 @@ __global__ void __launch_bounds__(TH * 32, TH == 16 ? 1 : 2) k_conv3x3_bf16(cons
         unsigned po;
         if constexpr (POFF_TABLE) po = poff[k];
         else po = piece_off(k, tid_c);
-        const float* src = (po != ~0u && !(DPX_BX_DBG & 32)) ? cb + po : zero_block;
-        if (DPX_BX_DBG & 64) src = inb + (tid & 63) * 4;
+        const float* src = po != ~0u ? cb + po : zero_block;
         dpx_glds16(src, (PRE ? smem_bx + (c & 1) * LAND_BYTES : land) + (k * NT + wv * 64) * 16);
       }
     }
   };
   auto issue_w = [&](int slot_idx) {                                  // global slot index = chunk * 3 + tap group
-    if (DPX_BX_DBG & 8) return;
     const char* src = wpk + (size_t)slot_idx * SLOTB + lane * 16;
     char* dst = ring + (slot_idx & 1) * SLOTB;
     for (int i = wv; i < SLOTB / 1024; i += NWV) dpx_glds16(src + i * 1024, dst + i * 1024);
@@ -246,24 +237,20 @@ __global__ void __launch_bounds__(TH * 32, TH == 16 ? 1 : 2) k_conv3x3_bf16(cons
   float f16_max = 0.f;                                                // split-f16: largest |operand| this thread has split
 
   const int nslots = chunks * 3;
-  if (!(DPX_BX_DBG & 4)) {
-    issue_act(0);
-    issue_w(0);
-  }
+  issue_act(0);
+  issue_w(0);
   for (int c = 0; c < chunks; ++c) {
     // ---- the chunk's activations: landed -> split into bf16 planes ------------------------------------------------------
     DPX_BX_STAMP(1 + c * 8);
-    if (!(DPX_BX_DBG & 4)) {
-    if (!(DPX_BX_DBG & 16)) dpx_wait_vm<0>();
+    dpx_wait_vm<0>();
     DPX_BX_STAMP(2 + c * 8);
     DPX_LDS_BARRIER();                                                // landing buffer complete; everybody is done with the old tile
-    }
     DPX_BX_STAMP(3 + c * 8);
     if constexpr (PRE) {
       tile = smem_bx + (c & 1) * LAND_BYTES;                       // landed as the operand planes themselves; the other tile is free:
       if (c + 1 < chunks) issue_act(c + 1);                           // every wave has left chunk c - 1 (barrier above)
     }
-    for (int u = tid; u < ((PRE || (DPX_BX_DBG & 2)) ? 0 : UNITS); u += NT) {
+    for (int u = tid; u < (PRE ? 0 : UNITS); u += NT) {
       const float4 lo4 = *(const float4*)(land + u * 32), hi4 = *(const float4*)(land + u * 32 + 16);
       const float v[8] = {lo4.x, lo4.y, lo4.z, lo4.w, hi4.x, hi4.y, hi4.z, hi4.w};
       if constexpr (MODE == 3) {
@@ -294,19 +281,19 @@ __global__ void __launch_bounds__(TH * 32, TH == 16 ? 1 : 2) k_conv3x3_bf16(cons
         *(uint4*)(tile + 2 * PLANE_BYTES + u * 16) = make_uint4(pack_hi16(l[0], l[1]), pack_hi16(l[2], l[3]), pack_hi16(l[4], l[5]), pack_hi16(l[6], l[7]));
     }
     DPX_BX_STAMP(4 + c * 8);
-    if (!PRE && !(DPX_BX_DBG & 4)) {
-    DPX_LDS_BARRIER();                                                // tile ready, landing buffer free
-    if (c + 1 < chunks) issue_act(c + 1);
+    if (!PRE) {
+      DPX_LDS_BARRIER();                                              // tile ready, landing buffer free
+      if (c + 1 < chunks) issue_act(c + 1);
     }
     DPX_BX_STAMP(5 + c * 8);
     // ---- three slots of three taps ----------------------------------------------------------------------------------------
     for (int tg = 0; tg < 3; ++tg) {
       const int s = c * 3 + tg;
-      if (tg > 0 && !(DPX_BX_DBG & 4)) {                               // (tg == 0: the barrier pair above already covered slot s)
-        if (!(DPX_BX_DBG & 16)) dpx_wait_vm<0>();
+      if (tg > 0) {                                                   // (tg == 0: the barrier pair above already covered slot s)
+        dpx_wait_vm<0>();
         DPX_LDS_BARRIER();                                            // slot s landed; slot s - 1 no longer read by anybody
       }
-      if (s + 1 < nslots && !(DPX_BX_DBG & 4)) issue_w(s + 1);
+      if (s + 1 < nslots) issue_w(s + 1);
       DPX_BX_STAMP(6 + tg + c * 8);
       const char* wslot = ring + (s & 1) * SLOTB;
 #pragma unroll
@@ -315,7 +302,7 @@ __global__ void __launch_bounds__(TH * 32, TH == 16 ? 1 : 2) k_conv3x3_bf16(cons
         uint4 bf[2][NPL];
 #pragma unroll
         for (int r = 0; r < 2; ++r) {
-          const int u = (DPX_BX_DBG & 1) ? (kg * ROWS + 2 * wv + r) * BX_COLS + n : (kg * ROWS + 2 * wv + r + dy) * BX_COLS + n + dx;
+          const int u = (kg * ROWS + 2 * wv + r + dy) * BX_COLS + n + dx;
 #pragma unroll
           for (int p = 0; p < NPL; ++p) bf[r][p] = *(const uint4*)(tile + p * PLANE_BYTES + u * 16);
         }
@@ -323,7 +310,7 @@ __global__ void __launch_bounds__(TH * 32, TH == 16 ? 1 : 2) k_conv3x3_bf16(cons
         for (int mt = 0; mt < MT; ++mt) {
           uint4 af[NPL];
 #pragma unroll
-          for (int p = 0; p < NPL; ++p) af[p] = *(const uint4*)(wslot + ((DPX_BX_DBG & 1) ? 0 : t3 * TAPB) + ((p * 2 + kg) * M32 + mt * 32 + n) * 16);
+          for (int p = 0; p < NPL; ++p) af[p] = *(const uint4*)(wslot + t3 * TAPB + ((p * 2 + kg) * M32 + mt * 32 + n) * 16);
           if constexpr (MODE == 3) {
             // (an accumulator is written again four matrix instructions later: no wait for the previous result)
             accx[mt][0] = mfma_f16(af[1], bf[0][0], accx[mt][0]);     // wl ah   (x 2^11)
@@ -808,7 +795,8 @@ extern "C" int dpx_ffdnet_forward_bf16(const float* x, float* y, const float* si
 // network_ffdnet.py:54-68 with autograd).  Forward pass that KEEPS every layer's output (C8, the backward pass's ReLU masks), weights
 // of the backward-data layers (flipped / transposed, split like the forward ones, no bias), and the backward pass: the same
 // k_conv3x3_bf16 on those weights with [a_l > 0] applied in the epilogue.  Gradients can be tiny (1e-7 of an MSE loss): the backward
-// pass always runs split-bf16 (mode 6, fp32's range); the forward pass may be any fp32-accurate mode.
+// pass runs split-bf16 (mode 6, fp32's range) or split-f16 on gradients scaled by a power of two (mode 3, watched by the range trap --
+// dpx_ffdnet_backward_bf16); the forward pass may be any fp32-accurate mode.
 extern "C" size_t dpx_ffdnet_bf16_acts_bytes(int B, int in_nc, int nc, int nb, int H, int W) {
   const size_t H2 = (H + 1) / 2, W2 = (W + 1) / 2, px = (size_t)B * H2 * W2;
   return (px * 8 * groups16(4 * in_nc + 1) + (size_t)(nb - 1) * px * 8 * groups16(nc) + px * 8 * groups16(4 * in_nc)) * sizeof(float);

@@ -627,8 +627,7 @@ static int il_seqs(const Plan1D& plan) {
 // twiddle gather and two barriers, and the waves of a CU walk it in step.
 // (the loops of run-time length below issue their global loads in batches of UB: written one element at a time, each iteration waits for
 //  its own load -- M / NT dependent round trips per phase, which is what a one-wave workgroup's row kernel then consists of)
-// TWL (both row kernels, as in k_cols_il): the M twiddles of the transform in shared memory behind the rows
-template <bool EVEN, int CT, int NT, bool TWL>
+template <bool EVEN, int CT, int NT>
 __global__ void __launch_bounds__(NT, 4) k_rows_r2c_il(const float* __restrict__ x, float2* __restrict__ spec, int W, int nrows, Plan1D plan,
                                                        const float2* __restrict__ twW) {
   HIP_DYNAMIC_SHARED(float2, smem)
@@ -637,14 +636,6 @@ __global__ void __launch_bounds__(NT, 4) k_rows_r2c_il(const float* __restrict__
   const int M = plan.n, Ws = (W + 1) / 2;
   float2* a = smem;
   const int tid = threadIdx.x;
-  const float2* twp = twW;
-  int tsc = EVEN ? 2 : 1;
-  if constexpr (TWL) {
-    float2* tl = smem + (size_t)M * LD;
-    for (int i = tid; i < M; i += NT) tl[i] = twW[i * tsc];
-    twp = tl;
-    tsc = 1;
-  }
   const int row0 = blockIdx.x * CT;
   const int nseq = min(CT, nrows - row0);
 #pragma unroll
@@ -666,7 +657,7 @@ __global__ void __launch_bounds__(NT, 4) k_rows_r2c_il(const float* __restrict__
     }
   }
   __syncthreads();
-  fft_il<-1, CT, NT>(a, plan, twp, tsc, tid);
+  fft_il<-1, CT, NT>(a, plan, twW, EVEN ? 2 : 1, tid);
 #pragma unroll
   for (int s = 0; s < CT; ++s) {
     if (s >= nseq) break;
@@ -703,7 +694,7 @@ __global__ void __launch_bounds__(NT, 4) k_rows_r2c_il(const float* __restrict__
   }
 }
 
-template <bool EVEN, int CT, int NT, bool TWL>
+template <bool EVEN, int CT, int NT>
 __global__ void __launch_bounds__(NT, 4) k_rows_c2r_il(const float2* __restrict__ spec, float* __restrict__ y, int W, int nrows, Plan1D plan,
                                                        const float2* __restrict__ twW, float scale) {
   HIP_DYNAMIC_SHARED(float2, smem)
@@ -712,14 +703,6 @@ __global__ void __launch_bounds__(NT, 4) k_rows_c2r_il(const float2* __restrict_
   const int M = plan.n, Ws = (W + 1) / 2;
   float2* a = smem;
   const int tid = threadIdx.x;
-  const float2* twp = twW;
-  int tsc = EVEN ? 2 : 1;
-  if constexpr (TWL) {
-    float2* tl = smem + (size_t)M * LD;
-    for (int i = tid; i < M; i += NT) tl[i] = twW[i * tsc];
-    twp = tl;
-    tsc = 1;
-  }
   DPX_ROWSTAMP(0);
   const int row0 = blockIdx.x * CT;
   const int nseq = min(CT, nrows - row0);
@@ -792,7 +775,7 @@ __global__ void __launch_bounds__(NT, 4) k_rows_c2r_il(const float2* __restrict_
   }
   __syncthreads();
   DPX_ROWSTAMP(1);
-  fft_il<+1, CT, NT>(a, plan, twp, tsc, tid);
+  fft_il<+1, CT, NT>(a, plan, twW, EVEN ? 2 : 1, tid);
   DPX_ROWSTAMP(6);
 #pragma unroll
   for (int s = 0; s < CT; ++s) {
@@ -1488,24 +1471,38 @@ static int masked_normal_apply_wave(float* p, const float* r, const float* beta,
 // host side
 // ---------------------------------------------------------------------------------------------
 
-static int rows_per_block(int M) {
-  int r = 4096 / (M + 1);
-  if (r < 1) r = 1;
-  if (r > 16) r = 16;
-  return r;
+constexpr size_t LDS_CU_BYTES = 160 * 1024;       // a CU's LDS: bounds a workgroup of the launches that opt in (DPX_LAUNCH_LDS)
+constexpr size_t LDS_PLAIN_BYTES = 64 * 1024;     // bounds a workgroup of the transforms launched without the opt-in (dpx_cfft2, the masked normal operator)
+
+// The launch geometry of the LDS-resident (first-form) transforms, in one place: a row workgroup holds `rpb` rows of length M, a column
+// workgroup `ct` columns of length H, each in two buffers (the passes ping-pong) of sequences padded by one element.
+static size_t lds_seq_bytes(int nseq, int len) { return (size_t)2 * nseq * (len + 1) * sizeof(float2); }
+struct LdsGeom {
+  int rpb, ct;              // rows per row workgroup (4096 points, 1 .. 16), columns per column workgroup (60 KB, 1 .. 16)
+  size_t shrow, shcol;      // shared memory of a row / a column workgroup
+  bool fits(size_t limit) const { return shrow <= limit && shcol <= limit; }
+};
+static LdsGeom lds_geom(int M, int H) {
+  const auto clamp16 = [](long v) { return (int)(v < 1 ? 1 : (v > 16 ? 16 : v)); };
+  LdsGeom g;
+  g.rpb = clamp16(4096 / (M + 1));
+  g.ct = clamp16((long)(60 * 1024 / lds_seq_bytes(1, H)));
+  g.shrow = lds_seq_bytes(g.rpb, M);
+  g.shcol = lds_seq_bytes(g.ct, H);
+  return g;
 }
 
 template <bool EVEN, int CT, int NT>
 static void launch_rows_il_t(bool fwd, const float* x, float2* spec, float* y, int W, int nrows, const Plan1D& prow, const float2* twW, hipStream_t s) {
   const size_t sh = (size_t)prow.n * (CT > 1 ? CT + 1 : 1) * sizeof(float2);
   const dim3 grid((nrows + CT - 1) / CT);
-  // (TWL = false: measured on the one-wave row workgroups, the table copy halves the workgroups a CU holds and costs more than the gathers it
-  //  saves -- 8 x 3 x 1000 x 1000: 62.9 -> 68.5 us, 1080 x 1920: 113 -> 170 us; four one-wave rows per workgroup around ONE shared copy were measured too: 64.7 -> 71 us;
-  //  the instantiation stays for A/B builds)
+  // (the row kernels gather their twiddles from the table in global memory, unlike k_cols_il: measured on the one-wave row workgroups, a copy of
+  //  the table in shared memory halves the workgroups a CU holds and costs more than the gathers it saves -- 8 x 3 x 1000 x 1000: 62.9 -> 68.5 us,
+  //  1080 x 1920: 113 -> 170 us; four one-wave rows per workgroup around ONE shared copy were measured too: 64.7 -> 71 us)
   if (fwd)
-    DPX_LAUNCH_LDS("k_rows_r2c_il", (k_rows_r2c_il<EVEN, CT, NT, false>), grid, dim3(NT), sh, s, x, spec, W, nrows, prow, twW);
+    DPX_LAUNCH_LDS("k_rows_r2c_il", (k_rows_r2c_il<EVEN, CT, NT>), grid, dim3(NT), sh, s, x, spec, W, nrows, prow, twW);
   else
-    DPX_LAUNCH_LDS("k_rows_c2r_il", (k_rows_c2r_il<EVEN, CT, NT, false>), grid, dim3(NT), sh, s, (const float2*)spec, y, W, nrows, prow, twW, 1.0f);
+    DPX_LAUNCH_LDS("k_rows_c2r_il", (k_rows_c2r_il<EVEN, CT, NT>), grid, dim3(NT), sh, s, (const float2*)spec, y, W, nrows, prow, twW, 1.0f);
 }
 // ct: 1 = one row per one-wave workgroup (row lengths up to 1024 complex points: the rule), 8 = eight rows interleaved on 512 threads (A/B),
 // 4 = four rows on 512 threads (lengths up to 2048)
@@ -1534,8 +1531,8 @@ static void launch_cols_il_t(float2* spec, const SpecArgs& A, int P, int C, int 
     longest = n > longest ? n : longest;
   }
   const dim3 grid(8 * longest);
-  // the twiddle table in shared memory when the workgroups per CU stay what they are without it (knob il_tw_lds = 0: never)
-  const size_t sh_tw = sh + (size_t)H * sizeof(float2), lds_cu = 160 * 1024;
+  // the twiddle table in shared memory (TWL) when a CU still holds two workgroups with it, or as many as without it where that is fewer
+  const size_t sh_tw = sh + (size_t)H * sizeof(float2), lds_cu = LDS_CU_BYTES;
   if (sh_tw <= lds_cu && lds_cu / sh_tw >= (lds_cu / sh > 2 ? 2 : lds_cu / sh)) {
     DPX_LAUNCH_LDS("k_cols_il", (k_cols_il<OP, CT, NT, true>), grid, dim3(NT), sh_tw, s, spec, A, C, H, W, pcol, twH, P);
     return;
@@ -1564,14 +1561,15 @@ static int spectral_apply(const float* x, float* y, int op, const SpecArgs& A, i
   const Plan1D prow = make_plan(M), pcol = make_plan(H);
   float2* spec = (float2*)ws;
   const int nrows = P * H;
-  const int rpb = rows_per_block(M);
-  const size_t shrow = (size_t)2 * rpb * (M + 1) * sizeof(float2);
+  const LdsGeom g = lds_geom(M, H);
+  const int rpb = g.rpb, CT = g.ct;
+  const size_t shrow = g.shrow, shcol = g.shcol;
   const dim3 grow((nrows + rpb - 1) / rpb);
   const int il = tune(TUNE_GENERIC_INTERLEAVED);          // 1 = rows and columns, 2 = rows only, 3 = columns only, 4 = both, rows eight to a workgroup (A/B)
   int rct = (il == 1 || il == 2 || il == 4) ? il_seqs(prow) : 0;
   const int cct = (il == 1 || il == 3 || il == 4) ? il_seqs(pcol) : 0;
   if (rct == 8 && il != 4) rct = 1;                      // a row per one-wave workgroup: no workgroup barrier, the waves of a CU drift apart
-  if (!rct && shrow > 160 * 1024) {
+  if (!rct && shrow > LDS_CU_BYTES) {
     set_error("row length %d too large for the LDS-resident generic FFT", W);
     return DPX_ERR_UNSUPPORTED;
   }
@@ -1584,11 +1582,7 @@ static int spectral_apply(const float* x, float* y, int op, const SpecArgs& A, i
     DPX_LAUNCH_LDS("k_rows_r2c", (k_rows_r2c<false>), grow, dim3(256), shrow, stream, x, spec, W, nrows, prow, tw_rows(table), rpb);
   if (cct) launch_cols_il(op, cct, spec, A, P, C, H, W, pcol, tw_cols(table, W), stream);
 
-  int CT = (int)(60 * 1024 / (2 * (size_t)(H + 1) * sizeof(float2)));
-  if (CT < 1) CT = 1;
-  if (CT > 16) CT = 16;
-  const size_t shcol = (size_t)2 * CT * (H + 1) * sizeof(float2);
-  if (!cct && shcol > 160 * 1024) {
+  if (!cct && shcol > LDS_CU_BYTES) {
     set_error("column length %d too large for the LDS-resident generic FFT", H);
     return DPX_ERR_UNSUPPORTED;
   }
@@ -1609,13 +1603,8 @@ static int spectral_apply(const float* x, float* y, int op, const SpecArgs& A, i
   return launch_status("spectral_apply");
 }
 
-// does a plane fit the LDS-resident transforms of masked_normal_apply?  (the same arithmetic as below)
-bool masked_normal_fits(int H, int W) {
-  const int rpb = rows_per_block(W);
-  int CT = (int)(60 * 1024 / (2 * (size_t)(H + 1) * sizeof(float2)));
-  CT = CT < 1 ? 1 : (CT > 16 ? 16 : CT);
-  return (size_t)2 * rpb * (W + 1) * sizeof(float2) <= 64 * 1024 && (size_t)2 * CT * (H + 1) * sizeof(float2) <= 64 * 1024;
-}
+// does a plane fit the LDS-resident transforms of masked_normal_apply?
+bool masked_normal_fits(int H, int W) { return lds_geom(W, H).fits(LDS_PLAIN_BYTES); }
 
 int masked_normal_apply(const float* p, float* Ap, float2* z, const float* mask2, int mask_images, const float* rho, float c, const int* done,
                         int B, int H, int W, const void* table, hipStream_t s) {
@@ -1629,12 +1618,10 @@ int masked_normal_apply(const float* p, float* Ap, float2* z, const float* mask2
                                          table, s, what);
   }
   const Plan1D prow = make_plan(W), pcol = make_plan(H);
-  const int rpb = rows_per_block(W);
-  const size_t shrow = (size_t)2 * rpb * (W + 1) * sizeof(float2);
-  int CT = (int)(60 * 1024 / (2 * (size_t)(H + 1) * sizeof(float2)));
-  CT = CT < 1 ? 1 : (CT > 16 ? 16 : CT);
-  const size_t shcol = (size_t)2 * CT * (H + 1) * sizeof(float2);
-  if (shrow > 64 * 1024 || shcol > 64 * 1024) {
+  const LdsGeom g = lds_geom(W, H);
+  const int rpb = g.rpb, CT = g.ct;
+  const size_t shrow = g.shrow, shcol = g.shcol;
+  if (!g.fits(LDS_PLAIN_BYTES)) {
     set_error("masked_normal_apply: plane %dx%d too large for the LDS-resident transform", H, W);
     return DPX_ERR_UNSUPPORTED;
   }
@@ -1653,15 +1640,14 @@ int masked_normal_apply(const float* p, float* Ap, float2* z, const float* mask2
 // ... and, for a small batch, few enough rows that the launch has a workgroup for every CU: these launches are latency-bound (4 x 320^2:
 // 1.6 MB), and 128 workgroups of 10 rows each walk every Stockham pass twice (400 butterflies on 256 threads) on half the chip.
 static int fused_rpb(int B, int H, int W) {
-  int r = rows_per_block(W);
+  int r = lds_geom(W, H).rpb;
   const int knob = tune(TUNE_CG_ROWS_PER_WG);
   if (knob > 0 && knob < r) r = knob;
   while (r > 1 && (H % r || (knob <= 0 && (long)B * H / r < 320))) --r;      // (measured at 4 x 320^2: 10 / 5 / 4 / 2 rows: 0.757 / 0.721 / 0.706 / 0.720 ms per outer iteration)
   return r;
 }
 static int fused_ct(int B, int H, int W) {
-  int CT = (int)(60 * 1024 / (2 * (size_t)(H + 1) * sizeof(float2)));
-  CT = CT < 1 ? 1 : (CT > 16 ? 16 : CT);
+  int CT = lds_geom(W, H).ct;
   const int knob = tune(TUNE_CG_COLS_PER_WG);
   if (knob > 0) return knob < CT ? knob : CT;
   while (CT > 4 && (long)B * ((W + CT - 1) / CT) < 320) --CT;      // (at least 4 columns = 32-byte pieces of a row; 11 / 8 / 5 / 4 columns: 0.737 / 0.720 / 0.714 / 0.706 ms)
@@ -1682,9 +1668,9 @@ int masked_normal_apply_fused(float* p, const float* r, float* Ap, float2* z, co
   }
   const Plan1D prow = make_plan(W), pcol = make_plan(H);
   const int rpb = fused_rpb(B, H, W);
-  const size_t shrow = (size_t)2 * rpb * (W + 1) * sizeof(float2);
+  const size_t shrow = lds_seq_bytes(rpb, W);
   const int CT = fused_ct(B, H, W);
-  const size_t shcol = (size_t)2 * CT * (H + 1) * sizeof(float2);
+  const size_t shcol = lds_seq_bytes(CT, H);
   const CgState S{state, B};
   const int* done = S.flags();
   const float scale = 1.0f / sqrtf((float)H * (float)W);
@@ -1737,14 +1723,14 @@ static size_t ds_ld(int n) { return (size_t)n + n / 8 + 1; }      // padded LDS 
 static int ds_ct(int H) {
   // two columns per workgroup (256 threads, two workgroups per CU: one loads while the other transforms) beat four (512 threads, one per
   // CU) at 8x3x1024^2: column pass 234 vs 267 us, row pass 164 vs 156 us (64-byte instead of 128-byte pieces)
-  return 2 * 2 * ds_ld(H) * sizeof(double2) <= 160 * 1024 ? 2 : 0;
+  return 2 * 2 * ds_ld(H) * sizeof(double2) <= LDS_CU_BYTES ? 2 : 0;
 }
 static int ds_rpb(int W) {
   const int M = (W % 2 == 0) ? W / 2 : W;
   // (measured at 8x3x1024^2, 256 threads: 2 rows per workgroup -- 4 workgroups per CU -- 174 us, 4 rows 207 us, 1 row 225 us)
   for (int r = 2; r >= 1; r >>= 1)
     if ((size_t)r * 2 * ds_ld(M) * sizeof(double2) <= 40 * 1024) return r;
-  return 2 * ds_ld(M) * sizeof(double2) <= 160 * 1024 ? 1 : 0;
+  return 2 * ds_ld(M) * sizeof(double2) <= LDS_CU_BYTES ? 1 : 0;
 }
 static size_t ds_spec_elems(int P, int H, int W) {
   const int CT = ds_ct(H) ? ds_ct(H) : 4, Wh = W / 2 + 1;
@@ -1821,12 +1807,10 @@ extern "C" int dpx_cfft2(const void* in, void* out, int inverse, int centred, in
   DPX_REQUIRE(P > 0 && H > 0 && W > 0, "dpx_cfft2: bad shape");
   hipStream_t s = (hipStream_t)stream;
   const Plan1D prow = make_plan(W), pcol = make_plan(H);
-  const int rpb = rows_per_block(W);
-  const size_t shrow = (size_t)2 * rpb * (W + 1) * sizeof(float2);
-  int CT = (int)(60 * 1024 / (2 * (size_t)(H + 1) * sizeof(float2)));
-  CT = CT < 1 ? 1 : (CT > 16 ? 16 : CT);
-  const size_t shcol = (size_t)2 * CT * (H + 1) * sizeof(float2);
-  if (shrow > 64 * 1024 || shcol > 64 * 1024) {
+  const LdsGeom g = lds_geom(W, H);
+  const int rpb = g.rpb, CT = g.ct;
+  const size_t shrow = g.shrow, shcol = g.shcol;
+  if (!g.fits(LDS_PLAIN_BYTES)) {
     set_error("dpx_cfft2: plane %dx%d too large for the LDS-resident transform", H, W);
     return DPX_ERR_UNSUPPORTED;
   }

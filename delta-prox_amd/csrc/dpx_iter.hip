@@ -271,7 +271,7 @@ __global__ void __launch_bounds__(256, (M == 512 && NT >= 3) ? 1 : 2) k_iter_row
 // next: 2 x 100 MB at 8x3x1024^2, which the 256 MB Infinity Cache can hold); the dual variables come back a whole iteration
 // later and the data spectrum is re-read once per iteration -- streaming those past the caches (`nt`) leaves the cache to the
 // spectra.  Measured (12-variant matrix, gpurun_out/ab3.log): all plain 4692 it/s, this setting 5147 it/s.
-// (DPX_R_LDX / _LDU / _STU / _STX and the constants R_LDX ... R_STX: dpx_iter_dev.h)
+// (the constants R_LDX, R_LDU, R_STU, R_STX: dpx_iter_dev.h)
 // DUAL = false: half-quadratic splitting (TT.dual == 0, DPX_TERM_NO_DUAL) -- the duals are neither fetched nor stored (the general
 // kernel streams 16 of its 24 B per element for planes nobody reads: 36 -> 20 B per element and iteration with the column kernel);
 // every wait count below is the general one with the dual streams' operations taken out (NU = 0 terms with a dual).
@@ -795,10 +795,7 @@ bool pgd_rows_seq_pow2(const float2* sin, float2* sout, float* x, const float* k
 // Two rows are in flight per group (two staging areas): with one, a launch has ~8 MB outstanding, short of what 8 TB/s needs.
 //   after the awaited DMA of row q (issued in step q-2): the V (+1) spectrum stores of steps q-2 and q-1, where those steps produced
 //   a row, and the D pieces of row q+1 (issued in step q-1)
-#ifndef DPX_SEED_STX
-#define DPX_SEED_STX DPX_R_STX
-#endif
-constexpr int SEED_STX = DPX_SEED_STX;        // cache policy of the seed pass's spectrum stores (0 plain, 1 write-through, 2 nt)
+constexpr int SEED_STX = R_STX;               // cache policy of the seed pass's spectrum stores (0 plain, 1 write-through, 2 nt)
 struct SeedOps {
   int linop[DPX_MAX_TERMS];
   int n;

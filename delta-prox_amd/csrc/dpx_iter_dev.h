@@ -81,18 +81,7 @@ template <class F> static inline void dispatch_iter_variant(const IterVariant& v
 
 // Cache policy of the row kernels' four streams (dpx_common.h): spectrum in / u in (loads, 1 = nt), u out / spectrum out
 // (stores, 2 = nt); see the comment in front of k_iter_rows_seq (dpx_iter.hip).
-#ifndef DPX_R_LDX
-#define DPX_R_LDX 0
-#endif
-#ifndef DPX_R_LDU
-#define DPX_R_LDU 1
-#endif
-#ifndef DPX_R_STU
-#define DPX_R_STU 2
-#endif
-#ifndef DPX_R_STX
-#define DPX_R_STX 1       // the spectrum handed to the next kernel: write-through (`sc1`), nothing left dirty at the kernel boundary (+0.5 ... 1 %)
-#endif
-constexpr int R_LDX = DPX_R_LDX, R_LDU = DPX_R_LDU, R_STU = DPX_R_STU, R_STX = DPX_R_STX;
+constexpr int R_LDX = 0, R_LDU = 1, R_STU = 2;
+constexpr int R_STX = 1;  // the spectrum handed to the next kernel: write-through (`sc1`), nothing left dirty at the kernel boundary (+0.5 ... 1 %)
 
 }  // namespace dpx

@@ -343,11 +343,9 @@ __global__ void __launch_bounds__(MR_THREADS) k_minres_init(MrState st, int phas
 }
 
 // elements of a leading system per workgroup (up to the cap of 2048 workgroups per launch)
-#ifndef DPX_MR_BLOCK_ELEMS
-#define DPX_MR_BLOCK_ELEMS 4096
-#endif
+constexpr int MR_BLOCK_ELEMS = 4096;
 int mr_blocks(int G, long N, int K) {
-  long nb = (N * K + DPX_MR_BLOCK_ELEMS - 1) / DPX_MR_BLOCK_ELEMS;
+  long nb = (N * K + MR_BLOCK_ELEMS - 1) / MR_BLOCK_ELEMS;
   const long cap = G >= 2048 ? 1 : 2048 / G, floor_ = ((long)K + MR_THREADS - 1) / MR_THREADS;
   if (nb > cap) nb = cap;
   if (nb < floor_) nb = floor_;

@@ -85,9 +85,6 @@ __device__ __forceinline__ float dpx_ld_agent(const float* p) { return *p; }
 // "my stores have completed" (s_waitcnt) in front of an agent-scope ticket -- a full release fence writes the XCD's whole L2 back,
 // once per workgroup: measured 47 us on an 800-workgroup launch whose own work takes 9 us.  Only the last workgroup pays an acquire
 // (L2 invalidate) before it reads the others' results with plain loads.
-#ifndef DPX_LAST_BLOCK_FULL_FENCE
-#define DPX_LAST_BLOCK_FULL_FENCE 0
-#endif
 __device__ __forceinline__ void dpx_st_agent(float* p, float v) {
 #ifdef DPX_EMULATED
   *p = v;
@@ -113,8 +110,7 @@ __device__ __forceinline__ bool dpx_last_block(unsigned* counter, unsigned nbloc
   __syncthreads();
   return *sh_flag != 0;
 #else
-  if (DPX_LAST_BLOCK_FULL_FENCE) __threadfence();
-  else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
   if (threadIdx.x == 0) {
     const unsigned ticket = __hip_atomic_fetch_add(counter, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);

@@ -26,12 +26,6 @@
 // (197 us on random data, whose matrix instructions draw more power: 248 TFLOP/s fp32-equivalent), split-bf16 266 us; DESIGN.md section 8.
 #pragma once
 
-// Tuning probes (wrong results by design; tools/build_variant.sh <name> -DDPX_WC_DBG=<bits>): 1 no matrix phase, 2 no split pass, 4 no partial-sum
-// stores, 8 no LDS-DMA
-#ifndef DPX_WC_DBG
-#define DPX_WC_DBG 0
-#endif
-
 namespace dpx {
 
 // Tuning aid (tools/build_variant_one.sh wc_trace dpx_wgrad_c8 -DDPX_WC_TRACE; never in the shipped library): the waves of workgroup 40 stamp the shader
@@ -192,7 +186,7 @@ __global__ void __launch_bounds__(WC_NW * 64, 1) k_wgrad_c8(const float* __restr
   const size_t plane8 = (size_t)H * W * 8;
   // piece p of this wave's share of job jb: p = 0 .. 2 the group rows k = wv + 8 p, p = 3 the outer pixels of its input groups
   auto issue_piece = [&](const Job& jb, int p) {
-    if ((DPX_WC_DBG & 8) || !jb.valid) return;
+    if (!jb.valid) return;
     char* const rawb = smem_wc;
     const int x0 = jb.xs * WC_WT;
     const int yac = min(max(jb.ya, 0), H - 1);
@@ -220,7 +214,6 @@ __global__ void __launch_bounds__(WC_NW * 64, 1) k_wgrad_c8(const float* __restr
   };
   // the split pass of this wave's landed group rows: lane = (piece j, pixel pair pp); fp32 pixel pair x 8 channels -> one dword per channel and plane
   auto split_own = [&](const Job& jb, int J) {
-    if (DPX_WC_DBG & 2) return;
     int lane_c = lane;
     DPX_OPAQUE(lane_c);                                     // (the item geometry is recomputed per pass: a dozen integer instructions against registers
     const int j = lane_c / 17, pp = lane_c - j * 17;        //  held across the matrix phase, whose 176 accumulators leave none to spare)
@@ -362,7 +355,7 @@ __global__ void __launch_bounds__(WC_NW * 64, 1) k_wgrad_c8(const float* __restr
     const int r0 = (J - 2) & 3, r1 = (J - 1) & 3, r2 = J & 3;
     auto slot_of = [&](int dy) { return dy == 0 ? r0 : (dy == 1 ? r1 : r2); };   // (selects: an indexed array would live in scratch memory)
 #pragma unroll
-    for (int ks = 0; ks < ((DPX_WC_DBG & 1) ? 0 : 2); ++ks) {
+    for (int ks = 0; ks < 2; ++ks) {
       if constexpr (BASE == MT && MT > 1) {
         unsigned ar[3][5];
         uint4 a0[3], a1[3], a2[3];
@@ -450,7 +443,7 @@ __global__ void __launch_bounds__(WC_NW * 64, 1) k_wgrad_c8(const float* __restr
   auto store_tile = [&](const f32x16& d, int mt, int nt, int tap) {
     float* t = dst + (size_t)((mt * NT + nt) * 9 + tap) * 1024 + lane * 4;
 #pragma unroll
-    for (int q = 0; q < ((DPX_WC_DBG & 4) ? 1 : 4); ++q) *(float4*)(t + q * 256) = make_float4(d[4 * q], d[4 * q + 1], d[4 * q + 2], d[4 * q + 3]);
+    for (int q = 0; q < 4; ++q) *(float4*)(t + q * 256) = make_float4(d[4 * q], d[4 * q + 1], d[4 * q + 2], d[4 * q + 3]);
   };
 #pragma unroll
   for (int i = 0; i < BASE; ++i) {

@@ -165,8 +165,8 @@ class FFDNet(RefKeyed):
         #               forward pass runs as "f16x2";
         #   "bf16"   -- plain bf16 operands, fp32 accumulation (bf16 training / inference mode, ~3e-3 relative).
         self.compute_mode = os.environ.get("DPX_FFDNET_MODE", "f16x2" if nc % 16 == 0 else "f32")
-        # trainable weights: False = forward / backward-data on the split kernels as with frozen weights (weight gradients: the f32-input GEMM
-        # on planar copies of their planes); True = everything on the f32-input kernels (the round-3 path, A/B)
+        # trainable weights: False = forward / backward-data on the split kernels as with frozen weights (weight gradients: k_wgrad_c8 on
+        # their C8 planes, in the backward pass's arithmetic -- dpx_ffdnet_backward_bf16_w); True = everything on the f32-input kernels (the round-3 path, A/B)
         self.train_f32 = bool(os.environ.get("DPX_FFDNET_TRAIN_F32"))
         # what happens when a "f16x2" forward meets an operand outside the binary16 range (a checkpoint with a large dynamic range):
         # "bf16x3" -- the enclosing solve() / denoise() is re-run on the split-bf16 arithmetic and the network keeps that mode
@@ -296,7 +296,7 @@ class FFDNet(RefKeyed):
             if self.compute_mode in ("bf16x3", "f16x2", "f16x2w") and self.nc % 16 == 0 and not (train_w and self.train_f32):
                 # forward and backward-data on the split kernels -- fp32-accurate, 2 - 3x the f32-input matrix instruction -- with frozen
                 # weights (unrolled plug-and-play training of schedules / upstream parameters) and with trainable ones (the weight-gradient
-                # GEMM is the f32-input kernel on planar copies of the split path's planes; `train_f32`: everything on the f32-input
+                # GEMM is k_wgrad_c8 on the split path's C8 planes, in the backward pass's arithmetic; `train_f32`: everything on the f32-input
                 # kernels, the round-3 path, for A/B)
                 self.last_train_path = "split"
                 return _FFDNetSplitFn.apply(self, x, sig_t, *params)

@@ -1553,8 +1553,8 @@ def case_ffdnet_split_backward(device, tiny=False):
             _assert_grad_close(x.grad.cpu().numpy() / np.float32(factor), res["f32"][1], f"split backward {shape} {fwd}/{bwd} x {factor}: d/dx", tol=1e-5)
             _assert_grad_close(sig.grad.cpu().numpy() / np.float32(factor), res["f32"][2], f"split backward {shape} {fwd}/{bwd} x {factor}: d/dsigma", tol=1e-5)
         col.model.compute_mode, col.model.backward_mode = "f16x2", "auto"
-        # trainable weights: forward / backward-data on the split kernels + the f32-input weight-gradient GEMM on planar copies of their
-        # C8 planes (dpx_ffdnet_backward_bf16_w) against everything on the f32-input kernels (dpx_ffdnet_backward): every layer's dW, db
+        # trainable weights: forward / backward-data on the split kernels + the weight-gradient GEMM on their C8 planes
+        # (k_wgrad_c8, dpx_ffdnet_backward_bf16_w) against everything on the f32-input kernels (dpx_ffdnet_backward): every layer's dW, db
         col.model.compute_mode = "f16x2"
         col.requires_grad_(True)
         wres = {}
@@ -1666,8 +1666,8 @@ def case_ffdnet_weight_grads(device):
     col = _ffdnet("color", device)
     col.train()
     x = T(g["wg_x"], device)
-    # both arithmetic paths of a trainable stack: forward / backward-data on the split kernels + the f32-input weight-gradient GEMM on
-    # planar copies of their planes (the default), and everything on the f32-input kernels (train_f32)
+    # both arithmetic paths of a trainable stack: forward / backward-data on the split kernels + the weight-gradient GEMM on their
+    # C8 planes, k_wgrad_c8 (the default), and everything on the f32-input kernels (train_f32)
     for f32 in (True, False):
         col.model.train_f32 = f32
         col.zero_grad()

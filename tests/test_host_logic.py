@@ -31,7 +31,7 @@ def test_c_abi_exports_every_declared_symbol():
 
 def test_no_shipped_kernel_uses_scratch_memory():
     """tools/spill_check.py over the compiler's resource remarks of every kernel of the library (kept by __graft_entry__.build()): a spilled
-    register in a shipped instantiation fails the suite; probe kernels behind debug knobs are exempt and listed there"""
+    register in any instantiation fails the suite"""
     import __graft_entry__
     __graft_entry__.build()
     sys.path.insert(0, os.path.join(ROOT, "tools"))
@@ -41,6 +41,22 @@ def test_no_shipped_kernel_uses_scratch_memory():
     for fam in ("k_iter_rows_par", "k_iter_rows_seq", "k_conv3x3_bf16", "k_conv3x3_wino", "k_cols_p2", "k_bwd_rows"):
         assert any(fam in r[1] for r in rows), fam
     assert spill_check.main() == 0
+
+
+def test_build_time_switches_of_the_kernels_are_the_listed_ones():
+    """The DPX_* macros that a preprocessor conditional of csrc tests are the emulator build, the trace builds and the two switches
+    whose value differs from file to file (set in front of the #include).  A switch nothing sets is a constant: an experiment that adds one adds it here."""
+    allowed = {"DPX_EMULATED", "DPX_PAR_TRACE", "DPX_WC_TRACE", "DPX_WN_TRACE", "DPX_PK_ASM", "DPX_FFT_BASEOFF"}
+    csrc = os.path.join(ROOT, "delta-prox_amd", "csrc")
+    files = [f for f in sorted(os.listdir(csrc)) if f.endswith((".hip", ".h"))]
+    assert len(files) > 30, files
+    tested = {}
+    for f in files:
+        text = open(os.path.join(csrc, f)).read().replace("\\\n", " ")
+        for line in re.findall(r"^[ \t]*#[ \t]*(?:if|ifdef|ifndef|elif)\b.*$", text, re.M):
+            for m in re.findall(r"\bDPX_\w+", line):
+                tested.setdefault(m, f)
+    assert set(tested) == allowed, {m: f for m, f in tested.items() if m not in allowed} or allowed - set(tested)
 
 
 def test_streaming_row_kernel_always_has_a_band_partition():

@@ -2,8 +2,7 @@
 """No kernel of the shipped library may use scratch memory (spilled registers).
 
 Reads the per-kernel resource remarks hipcc prints with -Rpass-analysis=kernel-resource-usage -- __graft_entry__.build() keeps them next to every
-object file (delta-prox_amd/build/*.o.resources.txt) -- and fails (exit status 1) if a kernel that is not a probe reports ScratchSize > 0.
-Probe kernels (wrong results by design) would be exempt -- k_cols_p2<..., DBG != 0>, k_cols_probe_* -- none is instantiated any more.
+object file (delta-prox_amd/build/*.o.resources.txt) -- and fails (exit status 1) if any kernel reports ScratchSize > 0.
 
     python tools/spill_check.py [-v]        (tools/spill_check.sh is the same call; tests/test_host_logic.py runs it)
 """
@@ -23,13 +22,6 @@ def demangle(names):
         return dict(zip(names, out))
     except Exception:
         return {n: n for n in names}
-
-
-def is_probe(name):
-    if "k_cols_probe" in name:
-        return True
-    m = re.match(r".*k_cols_p2<(\d+), (\d+), (\d+), (\d+), (\d+)>", name)
-    return bool(m) and int(m.group(5)) != 0
 
 
 def kernels():
@@ -54,12 +46,11 @@ def kernels():
 
 def main(verbose=False):
     rows = kernels()
-    bad = [r for r in rows if r[3] > 0 and not is_probe(r[1])]
-    probes = [r for r in rows if r[3] > 0 and is_probe(r[1])]
+    bad = [r for r in rows if r[3] > 0]
     if verbose:
         for src, n, v, s, sp in rows:
             print(f"{src:22s} vgprs {v:3d} scratch {s:4d}  {n.split('(')[0][:110]}")
-    print(f"spill_check: {len(rows)} kernels, {len(bad)} with scratch memory ({len(probes)} probe kernels with scratch are exempt)")
+    print(f"spill_check: {len(rows)} kernels, {len(bad)} with scratch memory")
     for src, n, v, s, sp in bad:
         print(f"  SCRATCH {s} bytes / lane ({sp} spilled registers): {src}: {n.split('(')[0]}")
     return 1 if bad else 0
