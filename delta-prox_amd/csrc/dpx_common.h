@@ -195,6 +195,16 @@ template <int NT> __device__ __forceinline__ float2 ld_stream(const float2* p) {
   else return *p;
 #endif
 }
+// 16 bytes (p 16-byte aligned), the same policies
+typedef float dpx_v4f __attribute__((ext_vector_type(4)));
+template <int NT> __device__ __forceinline__ float4 ld_stream16(const float4* p) {
+#ifdef DPX_EMULATED
+  return *p;
+#else
+  if constexpr (NT) return __builtin_bit_cast(float4, __builtin_nontemporal_load((const dpx_v4f*)p));
+  else return *p;
+#endif
+}
 
 // ---- bf16 history planes of the unrolled iteration (round to nearest even on the way in, exact on the way out) --------------------
 __device__ __forceinline__ unsigned dpx_bf16_bits(float x) {
@@ -329,6 +339,20 @@ bool pow2_path_available(int H, int W);
 constexpr int SPEC_TILE = 16;      // columns per spectrum tile of the power-of-two layout (16 = one 128-byte line per row; the column kernel needs it wider than its 8 columns per workgroup)
 __host__ __device__ __forceinline__ size_t spec_main_index(int tiled, int H, int Ws, int k, int l) {
   return tiled ? ((size_t)(l / SPEC_TILE) * H + k) * SPEC_TILE + (l % SPEC_TILE) : (size_t)k * Ws + l;
+}
+// COLUMN-PASS ORDER: the third layout, of the data spectrum (dpx_data_spectrum -> SpecArgs::add) on power-of-two planes alone.
+// Nothing but the column kernel k_cols_p2 reads that buffer, and thread tid = t COLS + c of the workgroup holding columns
+// [g COLS, (g + 1) COLS) always wants the same V = H / T values of it: the frequency rows t + krow(m) of its column c.  So they
+// are stored in that order, two of a thread's rows per 16-byte slot: per plane [Ws / COLS][V / 2][T COLS] slots, slot (g, j, tid)
+// holding rows t + krow(2j), t + krow(2j + 1) -- every wave load of the kernel is one linear 1 KB access, and no line is shared
+// between workgroups.  T and COLS are those of the k_cols_p2 instantiation of H (cols_dispatch checks them against these);
+// krow(m) = m T, and for H = 3 * 2^k (register m = r V/3 + a): (a T) + r H/3.  The footprint stays H Ws elements per plane.
+__host__ __device__ constexpr int cols_lanes(int H) { return H == 384 ? 16 : (H == 256 || H == 768) ? 32 : H == 2048 ? 128 : 64; }
+__host__ __device__ constexpr int cols_per_wg(int H) { return H == 2048 ? 4 : 8; }
+__host__ __device__ __forceinline__ size_t spec_cols_order_index(int H, int k, int l) {
+  const int T = cols_lanes(H), COLS = cols_per_wg(H), N = H % 3 == 0 ? H / 3 : H, VS = N / T;
+  const int r = k / N, kk = k - r * N, t = kk % T, m = r * VS + kk / T;      // k = t + krow(m)
+  return (size_t)(l / COLS) * H * COLS + ((size_t)(m / 2) * T * COLS + (size_t)t * COLS + l % COLS) * 2 + m % 2;
 }
 // table = all planes' main parts [C][H*Ws] followed by all side parts [C][H]
 // Power-of-two planes: the column kernel carries a plane's Nyquist column through its transforms as the

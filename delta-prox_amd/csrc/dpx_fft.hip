@@ -1029,7 +1029,7 @@ __global__ void __launch_bounds__(512) k_cols_fwd_f64(const double2* __restrict_
   // The workgroups whose columns share the 128-byte lines of the fp32 output / OTF table (16 columns = 16 / CT tiles) are given block
   // ids 8 apart inside a group of 8 * 16 / CT: the round-robin block -> XCD assignment puts them behind the same L2 at nearly the
   // same time, so a table line is fetched once instead of four times (measured: 609 MB of reads for 214 MB algorithmic before) and
-  // the four 32-byte pieces of an output line meet in that L2.
+  // the pieces of an output line meet in that L2 (column-pass order: a line holds two rows of 8 columns, i.e. of 8 / CT of these tiles).
   const int p = blockIdx.y;
   int lt;
   {
@@ -1082,7 +1082,8 @@ __global__ void __launch_bounds__(512) k_cols_fwd_f64(const double2* __restrict_
       }
       v = make_double2(v.x - n.y, v.y + n.x);          // packed: A + i B (power-of-two planes too, see dpx_common.h)
     }
-    float2* dst = o + spec_main_index(side_layout, H, Ws, k, l);
+    // (power-of-two planes: the tables are tile-major, the data spectrum is in the column pass's own order, dpx_common.h)
+    float2* dst = o + (side_layout ? spec_cols_order_index(H, k, l) : (size_t)k * Ws + l);
     if (accumulate) {
       const float2 old = *dst;
       *dst = make_float2((float)((double)old.x + v.x), (float)((double)old.y + v.y));

@@ -482,6 +482,7 @@ __device__ __forceinline__ void cols_body(const float2* __restrict__ spec_in, fl
   // before the last pass's arithmetic: ONE memory round trip between the two transforms, and with the spectra served
   // from the Infinity Cache the data spectrum is the HBM stream, so it starts one pass earlier (78.8 -> 76.0 us).
   static_assert((COLS == 8 || COLS == 4) && V % 2 == 0, "the table stage's lane map: 16-byte pieces of 8- or 4-column rows, two rows of a lane per piece");
+  static_assert(T == cols_lanes(H) && COLS == cols_per_wg(H), "the data spectrum is stored in this instantiation's lane order (spec_cols_order_index)");
   float2 av[V];                                       // data spectrum (SOLVE); MUL: the packed column's correction
 #pragma unroll
   for (int m = 0; m < V; ++m) av[m] = make_float2(0.f, 0.f);
@@ -508,11 +509,17 @@ __device__ __forceinline__ void cols_body(const float2* __restrict__ spec_in, fl
       }
     }
     if constexpr (OP == OP_SOLVE) {
-      unsigned offa = off0k;
+      // column-pass order (dpx_common.h): 16-byte slot j of this thread holds its rows t + krow(2j), t + krow(2j + 1) -- per wave
+      // instruction 1 KB of contiguous memory that no other workgroup touches
+      unsigned offa = sub_off * (unsigned)H + 2u * (unsigned)tid;
       DPX_OPAQUE(offa);
-      if (add) {
+      if (add) {      // (not also "&& !is_side", which is always true, k_cols_p2: tested here it costs the solve kernels 11 - 18 VGPRs)
 #pragma unroll
-        for (int m = 0; m < V; ++m) av[m] = ld_stream<COLS_ADD_NT>((const float2*)(add + (offa + step * krow(m)) * 8u));
+        for (int j = 0; j < V / 2; ++j) {
+          const float4 q = ld_stream16<COLS_ADD_NT>((const float4*)(add + (offa + (unsigned)(j * 2 * T * COLS)) * 8u));
+          av[2 * j] = make_float2(q.x, q.y);
+          av[2 * j + 1] = make_float2(q.z, q.w);
+        }
       }
     }
     DPX_CSTAMP(9);
@@ -561,7 +568,7 @@ __device__ __forceinline__ void cols_body(const float2* __restrict__ spec_in, fl
     unsigned offa = off0k;
     DPX_OPAQUE(offa);
     if (!is_side) {
-      if (add) dpx_wait_vm<V>();                        // the V data-spectrum loads of fetch_table may stay in flight
+      if (add) dpx_wait_vm<V / 2>();                    // the V / 2 data-spectrum loads of fetch_table may stay in flight
       else dpx_wait_vm<0>();
 #pragma unroll
       for (int m = 0; m < V; ++m) {
