@@ -1017,6 +1017,9 @@ extern "C" int dpx_admm_cg_pnp_iter(float* x, float* rhs, const float* ktb, cons
   DPX_REQUIRE(nterms >= 1 && nterms <= DPX_MAX_TERMS && ext >= 0 && ext < nterms && terms[ext].linop == DPX_LIN_IDENTITY,
               "dpx_admm_cg_pnp_iter: the prior must be a term on x itself");
   DPX_REQUIRE(in_nc == 1, "dpx_admm_cg_pnp_iter: a %d-channel network on single-channel images", in_nc);
+  for (int t = 0; t < nterms; ++t)                         // (the head pass evaluates every other term with prox_eval: closed forms only)
+    DPX_REQUIRE(t == ext || (terms[t].prox >= DPX_PROX_NORM1 && terms[t].prox <= DPX_PROX_SUMSQ),
+                "dpx_admm_cg_pnp_iter: term %d needs a closed-form prox (the prior is term %d)", t, ext);
   // the folded tail (and with it a prepared next right-hand side) needs the split kernels' C8 output, identity terms and the fused CG branch
   bool fold = mode != 0 && dpx::cg_masked_fft_is_fused(B) && tune(TUNE_PNP_CG_NO_FOLD) == 0;
   for (int t = 0; t < nterms; ++t) fold = fold && terms[t].linop == DPX_LIN_IDENTITY && terms[t].v && terms[t].u && !terms[t].u_out;

@@ -17,78 +17,60 @@
 
 namespace dpx {
 
-
 // ---------------------------------------------------------------------------------------------
-// z / dual update.  One thread = 4 consecutive pixels of a row (VEC=4) or one pixel (VEC=1).
+// The staged passes.  One thread = a pixel group (PixGroup<VEC>, dpx_prox_dev.h): 4 consecutive pixels of a row or one pixel.
 // ---------------------------------------------------------------------------------------------
-template <int VEC>
-__global__ void k_zupdate(const float* __restrict__ x, TermPack T, int B, int C, int H, int W) {
-  const int Wv = W / VEC;
-  const long total = (long)B * C * H * Wv;
-  for (long i = (long)xcd_block() * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
-    const int wv = (int)(i % Wv);
-    const long row = i / Wv;                 // (b*C + c)*H + h
-    const int h = (int)(row % H);
-    const long plane = row / H;
-    const int b = (int)(plane / C);
-    const long off = row * W + (long)wv * VEC;
-    float xv[VEC + 1];
-    if constexpr (VEC == 4) {
-      const float4 q = *(const float4*)(x + off);
-      xv[0] = q.x; xv[1] = q.y; xv[2] = q.z; xv[3] = q.w;
-    } else {
-      xv[0] = x[off];
-    }
+// x on a group with what the forward differences of the terms need beside it: the pixel to its right, the group below
+template <int VEC> struct XAt {
+  typename PixGroup<VEC>::V c, down;
+  float right = 0.f;
+  __device__ __forceinline__ XAt(const PixGroup<VEC>& G, const float* x, const TermPack& T) {
     bool need_w = false, need_h = false;
     for (int t = 0; t < T.n; ++t) {
       need_w |= T.t[t].linop == DPX_LIN_GRAD_W;
       need_h |= T.t[t].linop == DPX_LIN_GRAD_H;
     }
-    if (need_w) xv[VEC] = x[row * W + ((wv + 1) * VEC) % W];
-    float xd[VEC];
-    if (need_h) {
-      const long offd = (plane * H + (h + 1 == H ? 0 : h + 1)) * W + (long)wv * VEC;
-      if constexpr (VEC == 4) {
-        const float4 q = *(const float4*)(x + offd);
-        xd[0] = q.x; xd[1] = q.y; xd[2] = q.z; xd[3] = q.w;
-      } else {
-        xd[0] = x[offd];
-      }
-    }
+    c = G.ld(x, G.off);
+    if (need_w) right = x[G.right];
+    if (need_h) down = G.ld(x, G.down);
+  }
+};
+// (v - u) of a term on the VEC pixels at `at`, and rhs = ktb + r acc there
+template <int VEC> __device__ __forceinline__ void v_minus_u(const dpx_term& tm, long at, float* y) {
+  const auto a = PixGroup<VEC>::ld(tm.v, at), c = PixGroup<VEC>::ld(tm.u, at);
+#pragma unroll
+  for (int e = 0; e < VEC; ++e) y[e] = a.v[e] - c.v[e];
+}
+template <int VEC> __device__ __forceinline__ void rhs_store(float* rhs, const float* ktb, long at, float r, const float (&acc)[VEC]) {
+  const auto k = PixGroup<VEC>::ld0(ktb, at);
+  typename PixGroup<VEC>::V out;
+#pragma unroll
+  for (int e = 0; e < VEC; ++e) out.v[e] = fmaf(r, acc[e], k.v[e]);
+  PixGroup<VEC>::st(rhs, at, out);
+}
+// z / dual update
+template <int VEC>
+__global__ void k_zupdate(const float* __restrict__ x, TermPack T, int B, int C, int H, int W) {
+  const long total = (long)B * C * H * (W / VEC);
+  for (long i = (long)xcd_block() * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+    const PixGroup<VEC> G(i, C, H, W);
+    const XAt<VEC> xa(G, x, T);
     for (int t = 0; t < T.n; ++t) {
       const dpx_term tm = T.t[t];
-      const float lam = tm.lam ? tm.lam[b] * tm.alpha : 0.f;
-      float uu[VEC], vv[VEC];
-      if (tm.prox != DPX_PROX_EXTERNAL || true) {
-        if constexpr (VEC == 4) {
-          const float4 q = *(const float4*)(tm.u + off);
-          uu[0] = q.x; uu[1] = q.y; uu[2] = q.z; uu[3] = q.w;
-        } else {
-          uu[0] = tm.u[off];
-        }
-      }
+      const float lam = tm.lam ? tm.lam[G.b] * tm.alpha : 0.f;
+      typename PixGroup<VEC>::V uu = G.ld(tm.u, G.off), vv;
 #pragma unroll
       for (int e = 0; e < VEC; ++e) {
-        float kx;
-        if (tm.linop == DPX_LIN_IDENTITY) kx = xv[e];
-        else if (tm.linop == DPX_LIN_GRAD_W) kx = xv[e + 1] - xv[e];
-        else kx = xd[e] - xv[e];
-        const float d = kx + uu[e];
+        const float d = lin_K<VEC>(tm.linop, e, xa.c.v, xa.right, xa.down.v) + uu.v[e];
         if (tm.prox == DPX_PROX_EXTERNAL) {
-          vv[e] = d;                                         // the denoiser consumes d; u finished afterwards
+          vv.v[e] = d;                                       // the denoiser consumes d; u finished afterwards
         } else {
-          vv[e] = prox_eval(tm.prox, d, lam);
-          uu[e] = d - vv[e];
+          vv.v[e] = prox_eval(tm.prox, d, lam);
+          uu.v[e] = d - vv.v[e];
         }
       }
-      float* uo = tm.u_out ? tm.u_out : tm.u;            // out-of-place dual (differentiable mode keeps u_in)
-      if constexpr (VEC == 4) {
-        *(float4*)(tm.v + off) = make_float4(vv[0], vv[1], vv[2], vv[3]);
-        if (tm.prox != DPX_PROX_EXTERNAL) *(float4*)(uo + off) = make_float4(uu[0], uu[1], uu[2], uu[3]);
-      } else {
-        tm.v[off] = vv[0];
-        if (tm.prox != DPX_PROX_EXTERNAL) uo[off] = uu[0];
-      }
+      G.st(tm.v, G.off, vv);
+      if (tm.prox != DPX_PROX_EXTERNAL) G.st(tm.u_out ? tm.u_out : tm.u, G.off, uu);      // out-of-place dual: differentiable mode keeps u_in
     }
   }
 }
@@ -115,39 +97,24 @@ __global__ void k_rhs(float* __restrict__ rhs, const float* __restrict__ ktb, co
     for (int t = 0; t < T.n; ++t) {
       const dpx_term tm = T.t[t];
       float y[VEC + 1];   // y[1..VEC] = (v-u) at this pixel group, y[0] = left neighbour
-      if constexpr (VEC == 4) {
-        const float4 a = *(const float4*)(tm.v + off), c = *(const float4*)(tm.u + off);
-        y[1] = a.x - c.x; y[2] = a.y - c.y; y[3] = a.z - c.z; y[4] = a.w - c.w;
-      } else {
-        y[1] = tm.v[off] - tm.u[off];
-      }
+      v_minus_u<VEC>(tm, off, y + 1);
       if (tm.linop == DPX_LIN_IDENTITY) {
 #pragma unroll
         for (int e = 0; e < VEC; ++e) acc[e] += y[e + 1];
       } else if (tm.linop == DPX_LIN_GRAD_W) {
         const long left = row * W + (wv == 0 ? W - 1 : wv * VEC - 1);
-        y[0] = tm.v[left] - tm.u[left];
+        v_minus_u<1>(tm, left, y);
 #pragma unroll
         for (int e = 0; e < VEC; ++e) acc[e] += y[e] - y[e + 1];
       } else {
         const long offu = (plane * H + (h == 0 ? H - 1 : h - 1)) * W + (long)wv * VEC;
         float yu[VEC];
-        if constexpr (VEC == 4) {
-          const float4 a = *(const float4*)(tm.v + offu), c = *(const float4*)(tm.u + offu);
-          yu[0] = a.x - c.x; yu[1] = a.y - c.y; yu[2] = a.z - c.z; yu[3] = a.w - c.w;
-        } else {
-          yu[0] = tm.v[offu] - tm.u[offu];
-        }
+        v_minus_u<VEC>(tm, offu, yu);
 #pragma unroll
         for (int e = 0; e < VEC; ++e) acc[e] += yu[e] - y[e + 1];
       }
     }
-    if constexpr (VEC == 4) {
-      float4 k = ktb ? *(const float4*)(ktb + off) : make_float4(0.f, 0.f, 0.f, 0.f);
-      *(float4*)(rhs + off) = make_float4(fmaf(r, acc[0], k.x), fmaf(r, acc[1], k.y), fmaf(r, acc[2], k.z), fmaf(r, acc[3], k.w));
-    } else {
-      rhs[off] = fmaf(r, acc[0], ktb ? ktb[off] : 0.f);
-    }
+    rhs_store<VEC>(rhs, ktb, off, r, acc);
   }
 }
 
@@ -181,27 +148,20 @@ __global__ void k_zupdate_rhs(const float* __restrict__ x, float* __restrict__ r
     const long left = row * W + (wv == 0 ? W - 1 : wv * VEC - 1);                     // left neighbour of the group's first pixel
     const long offu = (plane * H + (h == 0 ? H - 1 : h - 1)) * W + (long)wv * VEC;      // the group one row up
     const float r = rho[b];
-    float xv[VEC + 1], xd[VEC], xu[VEC], xl = 0.f;
-    if constexpr (VEC == 4) {
-      const float4 q = *(const float4*)(x + off);
-      xv[0] = q.x; xv[1] = q.y; xv[2] = q.z; xv[3] = q.w;
-    } else {
-      xv[0] = x[off];
-    }
+    using G = PixGroup<VEC>;
+    using V = typename G::V;
+    float xv[VEC + 1], xl = 0.f;
+    V xd, xu;
+    const V xc = G::ld(x, off);
+#pragma unroll
+    for (int e = 0; e < VEC; ++e) xv[e] = xc.v[e];
     if (need_w) {
       xv[VEC] = x[row * W + ((wv + 1) * VEC) % W];
       xl = x[left];
     }
     if (need_h) {
       const long offd = (plane * H + (h + 1 == H ? 0 : h + 1)) * W + (long)wv * VEC;
-      if constexpr (VEC == 4) {
-        const float4 q = *(const float4*)(x + offd), p = *(const float4*)(x + offu);
-        xd[0] = q.x; xd[1] = q.y; xd[2] = q.z; xd[3] = q.w;
-        xu[0] = p.x; xu[1] = p.y; xu[2] = p.z; xu[3] = p.w;
-      } else {
-        xd[0] = x[offd];
-        xu[0] = x[offu];
-      }
+      xd = G::ld(x, offd), xu = G::ld(x, offu);
     }
     float acc[VEC];
 #pragma unroll
@@ -210,38 +170,24 @@ __global__ void k_zupdate_rhs(const float* __restrict__ x, float* __restrict__ r
       const dpx_term tm = T.t[t];
       const float lam = tm.lam ? tm.lam[b] * tm.alpha : 0.f;
       const bool nodual = tm.reserved & DPX_TERM_NO_DUAL;      // half-quadratic splitting: the incoming duals are zero and are not fetched
-      float uu[VEC], vv[VEC];
-      if (nodual) {
-#pragma unroll
-        for (int e = 0; e < VEC; ++e) uu[e] = 0.f;
-      } else if constexpr (VEC == 4) {
-        const float4 q = *(const float4*)(tm.u + off);
-        uu[0] = q.x; uu[1] = q.y; uu[2] = q.z; uu[3] = q.w;
-      } else {
-        uu[0] = tm.u[off];
-      }
+      V uu = nodual ? V{} : G::ld(tm.u, off), vv;
       float y[VEC + 1];   // y[1..VEC] = v - u' at this pixel group, y[0] = left neighbour (as in k_rhs)
 #pragma unroll
       for (int e = 0; e < VEC; ++e) {
         float kx;
         if (tm.linop == DPX_LIN_IDENTITY) kx = xv[e];
         else if (tm.linop == DPX_LIN_GRAD_W) kx = xv[e + 1] - xv[e];
-        else kx = xd[e] - xv[e];
-        const float d = kx + uu[e];
-        vv[e] = prox_eval(tm.prox, d, lam);
-        const float uin = uu[e];
-        uu[e] = d - vv[e];
-        y[e + 1] = vv[e] - (dual ? uu[e] : uin);            // (dual = 0: the duals are not advanced -- the next right-hand side sees the incoming ones)
+        else kx = xd.v[e] - xv[e];
+        const float d = kx + uu.v[e];
+        vv.v[e] = prox_eval(tm.prox, d, lam);
+        const float uin = uu.v[e];
+        uu.v[e] = d - vv.v[e];
+        y[e + 1] = vv.v[e] - (dual ? uu.v[e] : uin);            // (dual = 0: the duals are not advanced -- the next right-hand side sees the incoming ones)
       }
       // (v is read by nobody inside the loop -- the next right-hand side is formed here -- and duals that are not advanced go nowhere:
       //  emit_v = 0 / dual = 0 skip those stores; the caller's last z / dual stage, dpx_admm_zupdate, writes the final state)
-      if constexpr (VEC == 4) {
-        if (emit_v) *(float4*)(tm.v + off) = make_float4(vv[0], vv[1], vv[2], vv[3]);
-        if (dual) *(float4*)(tm.u_out + off) = make_float4(uu[0], uu[1], uu[2], uu[3]);
-      } else {
-        if (emit_v) tm.v[off] = vv[0];
-        if (dual) tm.u_out[off] = uu[0];
-      }
+      if (emit_v) G::st(tm.v, off, vv);
+      if (dual) G::st(tm.u_out, off, uu);
       if (tm.linop == DPX_LIN_IDENTITY) {
 #pragma unroll
         for (int e = 0; e < VEC; ++e) acc[e] += y[e + 1];
@@ -254,33 +200,20 @@ __global__ void k_zupdate_rhs(const float* __restrict__ x, float* __restrict__ r
 #pragma unroll
         for (int e = 0; e < VEC; ++e) acc[e] += y[e] - y[e + 1];
       } else {
-        float ua[VEC], yu[VEC];
-        if (nodual) {
-#pragma unroll
-          for (int e = 0; e < VEC; ++e) ua[e] = 0.f;
-        } else if constexpr (VEC == 4) {
-          const float4 q = *(const float4*)(tm.u + offu);
-          ua[0] = q.x; ua[1] = q.y; ua[2] = q.z; ua[3] = q.w;
-        } else {
-          ua[0] = tm.u[offu];
-        }
+        const V ua = nodual ? V{} : G::ld(tm.u, offu);
+        float yu[VEC];
 #pragma unroll
         for (int e = 0; e < VEC; ++e) {
-          const float d = (xv[e] - xu[e]) + ua[e];                        // the upper neighbour's own update, recomputed
+          const float d = (xv[e] - xu.v[e]) + ua.v[e];                        // the upper neighbour's own update, recomputed
           const float vu = prox_eval(tm.prox, d, lam);
           const float un = d - vu;
-          yu[e] = vu - (dual ? un : ua[e]);
+          yu[e] = vu - (dual ? un : ua.v[e]);
         }
 #pragma unroll
         for (int e = 0; e < VEC; ++e) acc[e] += yu[e] - y[e + 1];
       }
     }
-    if constexpr (VEC == 4) {
-      float4 k = ktb ? *(const float4*)(ktb + off) : make_float4(0.f, 0.f, 0.f, 0.f);
-      *(float4*)(rhs + off) = make_float4(fmaf(r, acc[0], k.x), fmaf(r, acc[1], k.y), fmaf(r, acc[2], k.z), fmaf(r, acc[3], k.w));
-    } else {
-      rhs[off] = fmaf(r, acc[0], ktb ? ktb[off] : 0.f);
-    }
+    rhs_store<VEC>(rhs, ktb, off, r, acc);
   }
 }
 
@@ -663,7 +596,8 @@ static int dot_blocks(long npb) {
   return (int)g;
 }
 
-static int pack_terms(TermPack& T, const dpx_term* terms, int n, const char* who, bool& vec_ok) {
+// vec: the launch rule so far (staged_vec on the caller's own planes); the terms' planes are added to it
+static int pack_terms(TermPack& T, const dpx_term* terms, int n, const char* who, int W, int& vec) {
   if (n < 0 || n > DPX_MAX_TERMS || (n > 0 && !terms)) {
     set_error("%s: nterms must be in [0, %d]", who, DPX_MAX_TERMS);
     return DPX_ERR_ARG;
@@ -679,7 +613,7 @@ static int pack_terms(TermPack& T, const dpx_term* terms, int n, const char* who
       set_error("%s: term %d has an unknown linop/prox code", who, i);
       return DPX_ERR_ARG;
     }
-    vec_ok &= aligned16({terms[i].v, terms[i].u, terms[i].u_out});
+    if (staged_vec(W, {terms[i].v, terms[i].u, terms[i].u_out}) != 4) vec = 1;
   }
   return DPX_OK;
 }
@@ -692,15 +626,13 @@ extern "C" int dpx_admm_zupdate(const float* x, const dpx_term* terms, int nterm
                                 dpx_stream_t stream) {
   DPX_REQUIRE(x && B > 0 && C > 0 && H > 0 && W > 0, "dpx_admm_zupdate: bad arguments");
   TermPack T;
-  bool vec = (W % 4 == 0) && aligned16({x});
-  int rc = pack_terms(T, terms, nterms, "dpx_admm_zupdate", vec);
+  int vec = staged_vec(W, {x});
+  int rc = pack_terms(T, terms, nterms, "dpx_admm_zupdate", W, vec);
   if (rc) return rc;
   if (nterms == 0) return DPX_OK;
   const long n = (long)B * C * H * W;
-  if (vec)
-    DPX_LAUNCH("k_zupdate", (k_zupdate<4>), dim3(grid_for8(n / 4, 256, 8192)), dim3(256), 0, (hipStream_t)stream, x, T, B, C, H, W);
-  else
-    DPX_LAUNCH("k_zupdate", (k_zupdate<1>), dim3(grid_for8(n, 256, 8192)), dim3(256), 0, (hipStream_t)stream, x, T, B, C, H, W);
+  DPX_LAUNCH_VEC(vec, "k_zupdate", (k_zupdate<4>), (k_zupdate<1>), dim3(grid_for8(n / vec, 256, 8192)), dim3(256), 0, (hipStream_t)stream, x, T, B, C, H,
+                 W);
   return launch_status("dpx_admm_zupdate");
 }
 
@@ -708,14 +640,11 @@ extern "C" int dpx_admm_rhs(float* rhs, const float* ktb, const float* rho, cons
                             int H, int W, dpx_stream_t stream) {
   DPX_REQUIRE(rhs && rho && B > 0 && C > 0 && H > 0 && W > 0, "dpx_admm_rhs: bad arguments");
   TermPack T;
-  bool vec = (W % 4 == 0) && aligned16({rhs, ktb});
-  int rc = pack_terms(T, terms, nterms, "dpx_admm_rhs", vec);
+  int vec = staged_vec(W, {rhs, ktb});
+  int rc = pack_terms(T, terms, nterms, "dpx_admm_rhs", W, vec);
   if (rc) return rc;
   const long n = (long)B * C * H * W;
-  if (vec)
-    DPX_LAUNCH("k_rhs", (k_rhs<4>), dim3(grid_for8(n / 4, 256, 8192)), dim3(256), 0, (hipStream_t)stream, rhs, ktb, rho, T, B, C, H, W);
-  else
-    DPX_LAUNCH("k_rhs", (k_rhs<1>), dim3(grid_for8(n, 256, 8192)), dim3(256), 0, (hipStream_t)stream, rhs, ktb, rho, T, B, C, H, W);
+  DPX_LAUNCH_VEC(vec, "k_rhs", (k_rhs<4>), (k_rhs<1>), dim3(grid_for8(n / vec, 256, 8192)), dim3(256), 0, (hipStream_t)stream, rhs, ktb, rho, T, B, C, H, W);
   return launch_status("dpx_admm_rhs");
 }
 
@@ -725,25 +654,19 @@ __global__ void k_rhs_fresh(float* __restrict__ rhs, const float* __restrict__ x
                             int H, int W) {
   const long total = (long)B * C * H * W;
   for (long i = (long)xcd_block() * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
-    const int w = (int)(i % W);
-    const long row = i / W;
-    const int h = (int)(row % H);
-    const long plane = row / H;
-    const float* p = x0 + plane * H * W;
-    const float c = p[(long)h * W + w];
+    const PixGroup<1> G(i, C, H, W);
+    const float c = x0[G.off];
     float acc = 0.f;
     for (int k = 0; k < nI; ++k) acc += c;
     if (nH) {
-      const float up = p[(long)(h ? h - 1 : H - 1) * W + w], dn = p[(long)(h + 1 < H ? h + 1 : 0) * W + w];
-      const float t = (c - up) - (dn - c);
+      const float t = (c - x0[G.up]) - (x0[G.down] - c);
       for (int k = 0; k < nH; ++k) acc += t;
     }
     if (nW) {
-      const float lf = p[(long)h * W + (w ? w - 1 : W - 1)], rt = p[(long)h * W + (w + 1 < W ? w + 1 : 0)];
-      const float t = (c - lf) - (rt - c);
+      const float t = (c - x0[G.left]) - (x0[G.right] - c);
       for (int k = 0; k < nW; ++k) acc += t;
     }
-    rhs[i] = rho[plane / C] * acc;
+    rhs[i] = rho[G.b] * acc;
   }
 }
 extern "C" int dpx_admm_rhs_fresh(float* rhs, const float* x0, const float* rho, const int* linops, int nterms, int B, int C, int H, int W,
@@ -766,8 +689,8 @@ extern "C" int dpx_admm_zupdate_rhs(const float* x, const dpx_term* terms, int n
                                     int dual, int emit_v, int B, int C, int H, int W, dpx_stream_t stream) {
   DPX_REQUIRE(x && rhs && rho_next && rhs != x && B > 0 && C > 0 && H > 0 && W > 0 && nterms > 0, "dpx_admm_zupdate_rhs: bad arguments");
   TermPack T;
-  bool vec = (W % 4 == 0) && aligned16({x, rhs, ktb});
-  int rc = pack_terms(T, terms, nterms, "dpx_admm_zupdate_rhs", vec);
+  int vec = staged_vec(W, {x, rhs, ktb});
+  int rc = pack_terms(T, terms, nterms, "dpx_admm_zupdate_rhs", W, vec);
   if (rc) return rc;
   for (int i = 0; i < nterms; ++i)
     DPX_REQUIRE(terms[i].prox != DPX_PROX_EXTERNAL && terms[i].u_out && terms[i].u_out != terms[i].u,
@@ -775,12 +698,8 @@ extern "C" int dpx_admm_zupdate_rhs(const float* x, const dpx_term* terms, int n
   for (int i = 0; i < nterms; ++i)
     DPX_REQUIRE(!(terms[i].reserved & DPX_TERM_NO_DUAL) || !dual, "dpx_admm_zupdate_rhs: DPX_TERM_NO_DUAL (term %d) excludes dual = 1", i);
   const long n = (long)B * C * H * W;
-  if (vec)
-    DPX_LAUNCH("k_zupdate_rhs", (k_zupdate_rhs<4>), dim3(grid_for8(n / 4, 256, 8192)), dim3(256), 0, (hipStream_t)stream, x, rhs, ktb, rho_next, T,
-               dual, emit_v, B, C, H, W);
-  else
-    DPX_LAUNCH("k_zupdate_rhs", (k_zupdate_rhs<1>), dim3(grid_for8(n, 256, 8192)), dim3(256), 0, (hipStream_t)stream, x, rhs, ktb, rho_next, T, dual,
-               emit_v, B, C, H, W);
+  DPX_LAUNCH_VEC(vec, "k_zupdate_rhs", (k_zupdate_rhs<4>), (k_zupdate_rhs<1>), dim3(grid_for8(n / vec, 256, 8192)), dim3(256), 0, (hipStream_t)stream, x,
+                 rhs, ktb, rho_next, T, dual, emit_v, B, C, H, W);
   return launch_status("dpx_admm_zupdate_rhs");
 }
 

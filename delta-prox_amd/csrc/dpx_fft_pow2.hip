@@ -14,6 +14,7 @@
 // transform.
 #include "dpx_dispatch.h"
 #include "dpx_fft_reg.h"
+#include "dpx_prox_dev.h"
 
 #include <cstdlib>
 #include <type_traits>
@@ -280,14 +281,6 @@ __global__ void __launch_bounds__(256) k_seed_rows(SeedTerms S_, const float* __
 }
 
 constexpr int PGD_LD_NT = 0, PGD_ST = 0;   // cache policy of k_pgd_rows' spectrum load / store (dpx_common.h)
-__device__ __forceinline__ float pgd_prox(int kind, float d, float lam) {     // (dpx_elementwise.hip::prox_eval, closed forms only)
-  if (kind == DPX_PROX_NORM1) {
-    const float m = fmaxf(fabsf(d) - lam, 0.f);
-    return d > 0.f ? m : (d < 0.f ? -m : 0.f * m);
-  }
-  if (kind == DPX_PROX_NONNEG) return fmaxf(d, 0.f);
-  return d / (1.f + 2.f * lam);
-}
 
 // One row pass of a proximal-gradient iteration (reference dprox/algo/pgd.py:26-54 with a circular-convolution data term):
 //   inverse row transform of the column-processed spectrum  (= K^T K x, the Gram operator is ONE multiply by |OTF|^2)
@@ -326,7 +319,7 @@ __global__ void __launch_bounds__(256) k_pgd_rows(const float2* __restrict__ spe
 #pragma unroll
   for (int m = 0; m < V; ++m) {
     float2 y = make_float2(xo[m].x - r * (v[m].x - kb[m].x), xo[m].y - r * (v[m].y - kb[m].y));
-    v[m] = make_float2(pgd_prox(prox, y.x, th), pgd_prox(prox, y.y, th));
+    v[m] = make_float2(prox_eval(prox, y.x, th), prox_eval(prox, y.y, th));
   }
   if (live) RM::store_pairs(xr, t, [&](int m) { return v[m]; });
   if (!spec_out) return;                                              // (block-uniform: the last iteration needs no spectrum)

@@ -161,12 +161,12 @@ __global__ void __launch_bounds__(256, (M == 512 && NT >= 3) ? 1 : 2) k_iter_row
           if (TT.vxu) {                                       // (kernel-uniform) t = q + x, d = K x + t, v = prox(d), q' = t - v, w = v - t
             const float tx = uu.x + xc[m].x, ty = uu.y + xc[m].y;
             dx = kx.x + tx, dy = kx.y + ty;
-            vx = prox1(tm.prox, dx, lam), vy = prox1(tm.prox, dy, lam);
+            vx = prox_eval(tm.prox, dx, lam), vy = prox_eval(tm.prox, dy, lam);
             ux = tx - vx, uy = ty - vy;
             w[m] = make_float2(-ux, -uy);
           } else {
             dx = fmaf(TT.dual, uu.x, kx.x), dy = fmaf(TT.dual, uu.y, kx.y);
-            vx = prox1(tm.prox, dx, lam), vy = prox1(tm.prox, dy, lam);
+            vx = prox_eval(tm.prox, dx, lam), vy = prox_eval(tm.prox, dy, lam);
             ux = dx - vx, uy = dy - vy;
             w[m] = make_float2(fmaf(-TT.dual, ux, vx), fmaf(-TT.dual, uy, vy));
           }
@@ -515,7 +515,7 @@ __global__ void __launch_bounds__(256, (NT >= 4 || (NT == 3 && VXU && M == 256))
           for (int m = 0; m < V; ++m) v[m] = make_float2(fmaxf(d[m].x, 0.f), fmaxf(d[m].y, 0.f));
         } else {
 #pragma unroll
-          for (int m = 0; m < V; ++m) v[m] = make_float2(prox1(DPX_PROX_SUMSQ, d[m].x, lam), prox1(DPX_PROX_SUMSQ, d[m].y, lam));
+          for (int m = 0; m < V; ++m) v[m] = make_float2(prox_eval(DPX_PROX_SUMSQ, d[m].x, lam), prox_eval(DPX_PROX_SUMSQ, d[m].y, lam));
         }
         float2 w[V];
 #pragma unroll
@@ -727,7 +727,7 @@ __global__ void __launch_bounds__(256, 2) k_pgd_rows_seq(const float2* __restric
 #pragma unroll
     for (int m = 0; m < V; ++m) {
       const float2 y = make_float2(xo[m].x - rr * (xa[m].x - kb[m].x), xo[m].y - rr * (xa[m].y - kb[m].y));
-      z[m] = make_float2(prox1(prox, y.x, th), prox1(prox, y.y, th));
+      z[m] = make_float2(prox_eval(prox, y.x, th), prox_eval(prox, y.y, th));
     }
     {
       float2* xw = (float2*)x + (unsigned)pl * H * M + (unsigned)h * M + t;

@@ -3,6 +3,7 @@
 #pragma once
 #include "dpx_dispatch.h"
 #include "dpx_fft_reg.h"
+#include "dpx_prox_dev.h"
 
 namespace dpx {
 
@@ -29,15 +30,6 @@ struct IterTerms {
                        // forward pass keeps it for the backward pass); like x_out / v_out an emit store, never counted in the waits
 };
 
-__device__ __forceinline__ float prox1(int kind, float d, float lam) {
-  if (kind == DPX_PROX_NORM1) {
-    const float m = fmaxf(fabsf(d) - lam, 0.f);
-    return d > 0.f ? m : (d < 0.f ? -m : 0.f * m);
-  }
-  if (kind == DPX_PROX_NONNEG) return fmaxf(d, 0.f);
-  return d / (1.f + 2.f * lam);
-}
-
 // Soft threshold of V pixel pairs, v = sign(d) max(|d| - lam, 0) (proxfn/norm.py), as  d - median(d, -lam, lam): one v_med3_f32 per
 // value and a packed subtraction per pair instead of the compare / select form's six vector instructions per value -- the same
 // values (d - lam and d + lam are the same single roundings as |d| - lam with the sign put back; inside the band d - d = 0).  The
@@ -55,7 +47,7 @@ template <int V> __device__ __forceinline__ void soft_threshold_pairs(const floa
     }
   } else {
 #pragma unroll
-    for (int m = 0; m < V; ++m) v[m] = make_float2(prox1(DPX_PROX_NORM1, d[m].x, lam), prox1(DPX_PROX_NORM1, d[m].y, lam));
+    for (int m = 0; m < V; ++m) v[m] = make_float2(prox_eval(DPX_PROX_NORM1, d[m].x, lam), prox_eval(DPX_PROX_NORM1, d[m].y, lam));
   }
 }
 

@@ -237,7 +237,7 @@ __global__ void __launch_bounds__(64 * NW, 1) k_iter_rows_par(const float2* __re
         for (int m = 0; m < V; ++m) v[m] = make_float2(fmaxf(d[m].x, 0.f), fmaxf(d[m].y, 0.f));
       } else {
 #pragma unroll
-        for (int m = 0; m < V; ++m) v[m] = make_float2(prox1(DPX_PROX_SUMSQ, d[m].x, lam), prox1(DPX_PROX_SUMSQ, d[m].y, lam));
+        for (int m = 0; m < V; ++m) v[m] = make_float2(prox_eval(DPX_PROX_SUMSQ, d[m].x, lam), prox_eval(DPX_PROX_SUMSQ, d[m].y, lam));
       }
       float2 w[V];
 #pragma unroll

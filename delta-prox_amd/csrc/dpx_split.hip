@@ -7,29 +7,14 @@
 // with K_i in {identity, grad_H, grad_W} that is a radius-2 circular stencil of x, v_i, u_i (or z_i).  One gather kernel evaluates
 // it per pixel (the neighbours come from L2 / the Infinity Cache: the planes were just streamed) instead of the 10-15 image passes
 // of the op-by-op formulation (forward stencil, AXPY, adjoint stencil, AXPY, adjoint stencil, AXPY per term).
-#include "dpx_common.h"
+#include "dpx_prox_dev.h"
 
 namespace dpx {
-
-struct SplitPack {
-  dpx_term t[DPX_MAX_TERMS];
-  int n;
-};
-
-__device__ __forceinline__ float split_prox(int kind, float d, float lam) {
-  if (kind == DPX_PROX_NORM1) {
-    const float m = fmaxf(fabsf(d) - lam, 0.f);
-    return d > 0.f ? m : (d < 0.f ? -m : 0.f * m);
-  }
-  if (kind == DPX_PROX_NONNEG) return fmaxf(d, 0.f);
-  if (kind == DPX_PROX_SUMSQ) return d / (1.f + 2.f * lam);
-  return d;
-}
 
 // MODE 0 (Pock-Chambolle): q_i = z_i (terms[i].v).   MODE 1 (linearised ADMM): q_i = (K_i x - v_i) + u_i.
 template <int MODE>
 __global__ void k_split_rhs(float* __restrict__ rhs, const float* __restrict__ ktb, const float* __restrict__ x, const float* __restrict__ rho,
-                            SplitPack T, int B, int C, int H, int W) {
+                            TermPack T, int B, int C, int H, int W) {
   const long total = (long)B * C * H * W;
   for (long i = (long)xcd_block() * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {      // (XCD-contiguous rows: dpx_common.h)
     const int w = (int)(i % W);
@@ -77,25 +62,20 @@ __global__ void k_split_rhs(float* __restrict__ rhs, const float* __restrict__ k
 }
 
 // Pock-Chambolle dual step, in place on z_i (terms[i].v):  z += r K_i xbar ;  z -= r prox_i(z, r * alpha)   with r = lam_i[b]
-__global__ void k_pc_dual(const float* __restrict__ xbar, SplitPack T, int B, int C, int H, int W) {
+__global__ void k_pc_dual(const float* __restrict__ xbar, TermPack T, int B, int C, int H, int W) {
   const long total = (long)B * C * H * W;
   for (long i = (long)xcd_block() * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {      // (XCD-contiguous rows: dpx_common.h)
-    const int w = (int)(i % W);
-    long r = i / W;
-    const int h = (int)(r % H);
-    const long pl = r / H;
-    const int b = (int)(pl / C);
-    const float* xp = xbar + pl * (long)H * W;
-    const float x0 = xp[(long)h * W + w];
+    const PixGroup<1> G(i, C, H, W);
+    const float x0 = xbar[G.off];
     for (int t = 0; t < T.n; ++t) {
       const dpx_term tm = T.t[t];
-      const float step = tm.lam ? tm.lam[b] : 0.f;
+      const float step = tm.lam ? tm.lam[G.b] : 0.f;
       float kx;
       if (tm.linop == DPX_LIN_IDENTITY) kx = x0;
-      else if (tm.linop == DPX_LIN_GRAD_H) kx = xp[(long)(h + 1 == H ? 0 : h + 1) * W + w] - x0;
-      else kx = xp[(long)h * W + (w + 1 == W ? 0 : w + 1)] - x0;
+      else if (tm.linop == DPX_LIN_GRAD_H) kx = xbar[G.down] - x0;
+      else kx = xbar[G.right] - x0;
       float z = tm.v[i] + step * kx;
-      z = z - step * split_prox(tm.prox, z, step * tm.alpha);
+      z = z - step * prox_eval(tm.prox, z, step * tm.alpha);
       tm.v[i] = z;
     }
   }
@@ -105,7 +85,7 @@ __global__ void k_pc_dual(const float* __restrict__ xbar, SplitPack T, int B, in
 
 using namespace dpx;
 
-static int split_pack(SplitPack& P, const dpx_term* terms, int nterms, int need_u, const char* who) {
+static int split_pack(TermPack& P, const dpx_term* terms, int nterms, int need_u, const char* who) {
   DPX_REQUIRE(terms && nterms >= 1 && nterms <= DPX_MAX_TERMS, "%s: 1..%d terms", who, DPX_MAX_TERMS);
   P.n = nterms;
   for (int i = 0; i < nterms; ++i) {
@@ -120,7 +100,7 @@ static int split_pack(SplitPack& P, const dpx_term* terms, int nterms, int need_
 extern "C" int dpx_split_rhs(float* rhs, const float* ktb, const float* x, const float* rho, const dpx_term* terms, int nterms, int mode,
                              int B, int C, int H, int W, dpx_stream_t stream) {
   DPX_REQUIRE(rhs && x && rho && rhs != x && B > 0 && C > 0 && H >= 3 && W >= 3 && (mode == 0 || mode == 1), "dpx_split_rhs: bad arguments");
-  SplitPack P;
+  TermPack P;
   const int rc = split_pack(P, terms, nterms, mode == 1, "dpx_split_rhs");
   if (rc) return rc;
   const long n = (long)B * C * H * W;
@@ -133,7 +113,7 @@ extern "C" int dpx_split_rhs(float* rhs, const float* ktb, const float* x, const
 
 extern "C" int dpx_pc_dual(const float* xbar, const dpx_term* terms, int nterms, int B, int C, int H, int W, dpx_stream_t stream) {
   DPX_REQUIRE(xbar && B > 0 && C > 0 && H > 0 && W > 0, "dpx_pc_dual: bad arguments");
-  SplitPack P;
+  TermPack P;
   const int rc = split_pack(P, terms, nterms, 0, "dpx_pc_dual");
   if (rc) return rc;
   for (int i = 0; i < nterms; ++i) DPX_REQUIRE(terms[i].prox >= DPX_PROX_NORM1 && terms[i].prox <= DPX_PROX_SUMSQ, "dpx_pc_dual: closed-form proxes only");

@@ -23,7 +23,7 @@
 // on the two-kernel loop, whose row kernel writes the non-last iterations' x, v_i and the next rhs into the slots as bf16 itself (nothing
 // but u_i and the spectra is read back by the next iteration): there only rhs(0) and u_i are work planes, and only rhs(0) and the last
 // iteration's x / v_i go through the packing kernel.  Both formats run the same two loops over one description of these places (FwdPlanes).
-#include "dpx_common.h"
+#include "dpx_prox_dev.h"
 
 using namespace dpx;
 
@@ -380,11 +380,12 @@ static int unrolled_backward_impl(const float* hist, const unsigned short* hist1
     }
     return first_rhs_stage(abuf[cur]);
   }
-  // ---- the loop with the rhs stage of iteration `it` and the z stage of iteration `it - 1` as ONE pass (k_rhs_z_bwd4, W % 4 == 0):
+  // ---- the loop with the rhs stage of iteration `it` and the z stage of iteration `it - 1` as ONE pass (k_rhs_z_bwd4, where staged_vec() gives 4):
   //        z(T-1) | solve(T-1) | [rhs(T-1) + z(T-2)] | solve(T-2) | ... | [rhs(1) + z(0)] | solve(0) | rhs(0)
   //      4 launches per iteration (3 of them the transform) + 1 finishing launch instead of 5 + 1, no g_v / g_u planes in between.
   //      Knob unroll_bwd_staged = 1 keeps the staged loop below (A/B and tests).
-  if (W % 4 == 0 && tune(TUNE_UNROLL_BWD_STAGED) != 1) {
+  //      (every plane of the loop sits a multiple of px elements into the history or the workspace: with W % 4 == 0 those two decide the rule)
+  if (tune(TUNE_UNROLL_BWD_STAGED) != 1 && staged_vec(W, {ws}, {hist ? (const void*)hist : hist16}, hb) == 4) {
     float* abuf[2] = {gu_a, gu_b};
     int cur = 0;
     // (experiment) the fused stage's last workgroup finishes the iteration's reductions itself (one arrival counter in the workspace's

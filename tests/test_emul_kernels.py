@@ -205,6 +205,130 @@ def test_unrolled_backward_shortest_loops():
     pc.case_unrolled_bwd_shortest_loops(DEV)
 
 
+def test_unrolled_plane_sizes_one_pixel_per_thread():
+    """widths with W % 4 = 2, 3 and 1, an odd height, two images x three channels: the forward pass runs the one-pixel forms of
+    k_zupdate_rhs / k_rhs / k_zupdate, the backward pass the one-pixel forms of the staged loop's stages"""
+    pc.case_unrolled_plane_sizes(DEV, shapes=((2, 3, 30, 46), (2, 3, 31, 43), (2, 3, 30, 41)))
+
+
+def test_unrolled_backward_shortest_loops_one_pixel_per_thread():
+    pc.case_unrolled_bwd_shortest_loops(DEV, shapes=((1, 2, 31, 43),))
+
+
+def _shifted(t, shift):
+    """a contiguous copy of t that starts `shift` floats into its (64-byte aligned) storage"""
+    import torch
+    buf = torch.empty(t.numel() + 4, dtype=torch.float32)
+    view = buf[shift:shift + t.numel()].view(t.shape)
+    view.copy_(t)
+    assert view.data_ptr() % 16 == 4 * shift
+    return view
+
+
+def test_staged_backward_passes_take_misaligned_planes():
+    """planes that start one float into their storage (W % 4 == 0: the width alone would pick the 16-byte forms) go through the one-pixel
+    forms of the staged backward passes: dpx_admm_zupdate_bwd, and the unrolled backward's staged loop -- selected by its knob, and as what
+    the image-domain fused stage falls back to (the launch log shows k_zupdate_bwd per iteration and no k_rhs_z_bwd; on aligned planes the
+    same setting does launch k_rhs_z_bwd) -- give the same planes bit for bit as on aligned planes, and per-image sums within 1e-5 (the
+    bound case_unrolled_bwd_fused_vs_staged uses between forms that add in different orders)"""
+    import os
+    import re
+    import ctypes
+    import numpy as np
+    import torch
+    import synthetic
+    from conftest import rel_l2
+    from dprox import _backend as be, _ops as ops
+    L = be.lib()
+    B, C, H, W = shape = (1, 2, 16, 24)
+    px = B * C * H * W
+
+    # ---- dpx_admm_zupdate_bwd
+    gen = torch.Generator().manual_seed(3)
+    codes = ((be.LIN_GRAD_H, be.PROX_NORM1, 1.0), (be.LIN_GRAD_W, be.PROX_NORM1, 1.0), (be.LIN_IDENTITY, be.PROX_NONNEG, 1.0),
+             (be.LIN_IDENTITY, be.PROX_SUMSQ, 0.5))
+    n = len(codes)
+    lam = [0.05 + 0.1 * torch.rand(B, generator=gen) for _ in codes]
+    vs = [ops.prox(pk, torch.randn(shape, generator=gen), lam[i], alpha=al) for i, (_, pk, al) in enumerate(codes)]
+    gvs, guns = ([torch.randn(shape, generator=gen) for _ in codes] for _ in range(2))
+    ws_floats = L.query("dpx_admm_bwd_ws_bytes", B, C, H, W) // 4
+
+    def zupdate_bwd(shift):
+        place = lambda t: _shifted(t, shift)
+        keep = [[place(t) for t in ts] for ts in (vs, gvs, guns)]
+        gx, ws, gus = place(torch.zeros(shape)), place(torch.zeros(ws_floats)), [place(torch.zeros(shape)) for _ in codes]
+        arr = (be.BwdTerm * n)()
+        for i, (lc, pk, al) in enumerate(codes):
+            arr[i].linop, arr[i].prox, arr[i].alpha, arr[i].lam = lc, pk, al, lam[i].data_ptr()
+            arr[i].v, arr[i].gv, arr[i].gu_new, arr[i].gu = keep[0][i].data_ptr(), keep[1][i].data_ptr(), keep[2][i].data_ptr(), gus[i].data_ptr()
+        glam = torch.empty(n, B)
+        L.call("dpx_admm_zupdate_bwd", be.ptr(gx), arr, n, be.ptr(glam), B, C, H, W, be.ptr(ws), be.stream())
+        return [gx, *gus], glam
+
+    (planes_a, sums_a), (planes_m, sums_m) = zupdate_bwd(0), zupdate_bwd(1)
+    for k, (a, m) in enumerate(zip(planes_a, planes_m)):
+        assert torch.equal(a, m), f"dpx_admm_zupdate_bwd: plane {k} differs on misaligned planes"
+    assert rel_l2(sums_m.numpy(), sums_a.numpy()) <= 1e-5
+
+    # ---- the unrolled backward's staged loop: the arguments of a real training step's call, replayed on buffers of our own
+    decl = re.search(r"\bdpx_admm_unrolled_backward\s*\(([^;]*?)\)\s*;", open(os.path.join(emul_util.ROOT, "include", "dpx.h")).read(), re.S).group(1)
+    names = [re.search(r"(\w+)\s*$", prm).group(1) for prm in decl.split(",")]       # the parameters' names, in the header's order
+
+    def launches():
+        buf = ctypes.create_string_buffer(1 << 16)
+        L.call("dpx_timing_report", buf, len(buf))
+        return {ln.split()[0]: int(ln.split()[1]) for ln in buf.value.decode().splitlines() if ln.split()}
+
+    def replay(args, shift, staged):
+        assert len(args) == len(names)
+        a = dict(zip(names, args))
+        n, T = a["nterms"], a["T"]
+        place = lambda t: _shifted(t, shift)
+        take = lambda p, count: torch.from_numpy(np.ctypeslib.as_array((ctypes.c_float * count).from_address(p.value)).copy())
+        hist = place(take(a["hist"], T * (2 + 2 * n) * px))
+        gx = None if a["gx"] is None else place(take(a["gx"], px).view(shape))
+        assert all(p is None for p in list(a["gv_in"]) + list(a["gu_in"])), "the loss uses x alone"
+        gv0, gu0 = ([place(torch.zeros(shape)) for _ in range(n)] for _ in range(2))
+        goff = [None if p is None else place(torch.zeros(shape)) for p in list(a["goff"])[:a["n_off"]]]
+        g_rho, g_lam = torch.empty(T, B), torch.empty(T, n, B)
+        ws = place(torch.zeros(L.query("dpx_admm_unrolled_bwd_ws_bytes", n, B, C, H, W) // 4))
+        ptrs = lambda ts: (ctypes.c_void_p * max(len(ts), 1))(*[None if t is None else t.data_ptr() for t in ts])
+        a.update(hist=be.ptr(hist), gx=be.ptr(gx), gv0=ptrs(gv0), gu0=ptrs(gu0), grho=be.ptr(g_rho), glam=be.ptr(g_lam), goff=ptrs(goff), ws=be.ptr(ws))
+        orig("dpx_timing_enable", 1)
+        try:
+            launches()                                       # (reading the log resets it)
+            with be.tuned(unroll_bwd_staged=staged):
+                orig("dpx_admm_unrolled_backward", *[a[k] for k in names])
+            log = launches()
+        finally:
+            orig("dpx_timing_enable", 0)
+        return [*gv0, *gu0, *[t for t in goff if t is not None]], torch.cat([g_rho.flatten(), g_lam.flatten()]), log, T
+
+    runs = []
+
+    def spy(name, *args):
+        if name == "dpx_admm_unrolled_backward" and not runs:
+            runs.extend([replay(args, 0, 1), replay(args, 1, 1), replay(args, 1, 2), replay(args, 0, 2)])
+        return orig(name, *args)
+
+    orig = L.call
+    L.call = spy
+    try:
+        pc._unrolled_bwd_run(DEV, synthetic.deconv_case(*shape, seed=17, ksize=5, ksigma=1.2), "tv+nn", "f32", 3, dict(unroll_bwd_staged=1))
+    finally:
+        del L.call
+    assert len(runs) == 4
+    (planes_a, sums_a, log_a, T), (planes_m, sums_m, log_m, _), (planes_f, sums_f, log_f, _), (_, _, log_fused, _) = runs
+    for log in (log_a, log_m, log_f):                        # the staged loop: one z stage per iteration, never the fused stage
+        assert log.get("k_zupdate_bwd") == T and "k_rhs_z_bwd" not in log, log
+    assert log_fused.get("k_rhs_z_bwd") == T - 1 and log_fused.get("k_zupdate_bwd") == 1, log_fused      # (aligned planes: the fused stage runs)
+    assert float(sums_a.abs().max()) > 0 and all(float(p.abs().max()) > 0 for p in planes_a)
+    for what, planes, sums in (("staged loop", planes_m, sums_m), ("staged loop in place of the fused stage", planes_f, sums_f)):
+        for k, (a, m) in enumerate(zip(planes_a, planes)):
+            assert torch.equal(a, m), f"{what}: plane {k} differs on misaligned planes"
+        assert rel_l2(sums.numpy(), sums_a.numpy()) <= 1e-5, what
+
+
 def test_unrolled_forward_refuses_fresh_x0_off_the_two_kernel_iteration():
     """both history formats: a lazy fresh state (fresh_x0) exists only for the two-kernel iteration; on a plane that is not on it the
     entry point says so and launches nothing (it used to be the fp32 entry's rule alone)"""

@@ -265,6 +265,16 @@ def test_unrolled_backward_shortest_loops():
     pc.case_unrolled_bwd_shortest_loops(DEV, shapes=((1, 2, 32, 48), (1, 1, 256, 256)))
 
 
+def test_unrolled_plane_sizes_one_pixel_per_thread():
+    """widths with W % 4 = 2, 3 and 1, an odd height, two images x three channels: the forward pass runs the one-pixel forms of
+    k_zupdate_rhs / k_rhs / k_zupdate, the backward pass the one-pixel forms of the staged loop's stages"""
+    pc.case_unrolled_plane_sizes(DEV, shapes=((2, 3, 30, 46), (2, 3, 31, 43), (2, 3, 30, 41)))
+
+
+def test_unrolled_backward_shortest_loops_one_pixel_per_thread():
+    pc.case_unrolled_bwd_shortest_loops(DEV, shapes=((1, 2, 31, 43),))
+
+
 def test_unrolled_gradients():
     pc.case_unrolled_grads(DEV)
 
