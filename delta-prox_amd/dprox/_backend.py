@@ -225,6 +225,11 @@ SIGNATURES = {
     "dpx_tv_ws_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int]),
     "dpx_tv_plan": (c_int, [c_int, c_int, c_int, c_int, c_int, POINTER(c_int)]),
     "dpx_tv_denoise": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "dpx_tv_codes_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int]),
+    "dpx_tv_denoise_rec": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "dpx_tv_bwd_ws_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int]),
+    "dpx_tv_bwd_plan": (c_int, [c_int, c_int, c_int, c_int, c_int, POINTER(c_int)]),
+    "dpx_tv_backward": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "dpx_anderson_ws_bytes": (c_size_t, [c_int, c_int, c_long]),
     "dpx_anderson_gram_row": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_long, c_void_p, c_void_p]),
     "dpx_anderson_mix": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_float, c_int, c_int, c_long, c_void_p]),

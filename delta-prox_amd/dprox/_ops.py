@@ -1175,18 +1175,79 @@ def tv_plan(shape, iters=5, axes=(1, 2)):
     return dict(steps=out[0], launches=out[1], tile=(out[2], out[3], out[4]), lds_bytes=out[5])
 
 
-def tv_denoise(v, lam, iters=5, axes=(1, 2)):
+def tv_bwd_plan(shape, iters=5, axes=(1, 2)):
+    """what dpx_tv_backward would do on an [N, C, H, W] cotangent: dict(steps, launches, tile, lds_bytes) (dpx_tv_bwd_plan)"""
+    _, D0, D1, D2 = (int(n) for n in shape)
+    out = (ctypes.c_int * 6)()
+    be.lib().call("dpx_tv_bwd_plan", D0, D1, D2, _tv_axes_mask(axes), int(iters), out)
+    return dict(steps=out[0], launches=out[1], tile=(out[2], out[3], out[4]), lds_bytes=out[5])
+
+
+def tv_denoise_rec(v, lam, iters, mask):
+    """the recording forward on a checked, contiguous volume and an [N] lam: (out, the clip states of dpx_tv_denoise_rec as uint8)"""
+    N, D0, D1, D2 = _shape4(v)
+    L = be.lib()
+    nb = L.query("dpx_tv_codes_bytes", N, D0, D1, D2, mask, int(iters))
+    codes = _bytes(nb, v.device)[:nb] if nb else None           # (kept by the autograd node: not the shared scratch of workspace())
+    ws = workspace("tv", L.query("dpx_tv_ws_bytes", N, D0, D1, D2, mask, int(iters)), v.device)
+    out = torch.empty_like(v)
+    L.call("dpx_tv_denoise_rec", ptr(v), ptr(out), ptr(lam), ptr(codes), N, D0, D1, D2, mask, int(iters), ptr(ws), be.stream())
+    return out, codes
+
+
+def tv_backward(g, codes, iters, mask, want_lam=True):
+    """(gy, glam [N] or None) of dpx_tv_backward for the cotangent g [N, C, H, W] and the states tv_denoise_rec recorded"""
+    g = require(g.contiguous(), what="tv_backward cotangent")
+    N, D0, D1, D2 = _shape4(g)
+    L = be.lib()
+    ws = workspace("tv_bwd", L.query("dpx_tv_bwd_ws_bytes", N, D0, D1, D2, mask, int(iters)), g.device)
+    gy = torch.empty_like(g)
+    glam = torch.empty(N, dtype=torch.float32, device=g.device) if want_lam else None
+    L.call("dpx_tv_backward", ptr(g), ptr(codes), ptr(gy), ptr(glam), N, D0, D1, D2, mask, int(iters), ptr(ws), be.stream())
+    return gy, glam
+
+
+class _TVDenoiseFn(torch.autograd.Function):
+    """ops.tv_denoise(..., differentiable=True) under autograd: the recording forward, its state bytes saved for dpx_tv_backward"""
+
+    @staticmethod
+    def forward(ctx, v, lam, lam_vec, iters, mask):
+        out, codes = tv_denoise_rec(v, lam_vec, iters, mask)
+        ctx.codes, ctx.iters, ctx.mask = codes, iters, mask
+        ctx.lam_shape = tuple(lam.shape) if isinstance(lam, torch.Tensor) else None
+        ctx.lam_device = lam.device if isinstance(lam, torch.Tensor) else None
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        want_lam = ctx.needs_input_grad[1]
+        gy, glam = tv_backward(g, ctx.codes, ctx.iters, ctx.mask, want_lam)
+        if want_lam:
+            N = glam.shape[0]
+            n_lam = int(np.prod(ctx.lam_shape)) if ctx.lam_shape else 1
+            glam = (glam if n_lam == N else glam.sum()).reshape(ctx.lam_shape).to(ctx.lam_device)     # (one lam for N images: their sum)
+        return (gy if ctx.needs_input_grad[0] else None), glam, None, None, None
+
+
+def tv_denoise(v, lam, iters=5, axes=(1, 2), differentiable=False):
     """anisotropic TV denoising of an [N, C, H, W] fp32 volume: `iters` projected dual-ascent steps (step 1/5, threshold lam / 2) with
     differences along the NCHW dims in `axes` -- the reference's TV_denoising ((1, 2): its 2-D form differences C and H) / TV_denoising3d
     ((1, 2, 3)) in one dpx_tv_denoise call; lam: per-image (0-d / [N]), >= 0 (checked where it is a host value; a device tensor is not
-    read back); forward-only; a new tensor"""
+    read back); a new tensor.
+
+    The gradient is opt-in.  With the default a call autograd would have to differentiate raises NotImplementedError (forward-only).
+    With ``differentiable=True`` such a call runs the recording forward (dpx_tv_denoise_rec: the same output bit for bit, plus the clip
+    state of every dual update, one byte per voxel and step -- (iters - 1) bytes per voxel kept until the backward pass, which is why it
+    has to be asked for) and its backward is dpx_tv_backward: the gradient to `v`, and to `lam` in lam's own shape where lam requires it.
+    A call that needs no gradient takes the plain forward and records nothing, whatever the flag."""
     if not isinstance(v, torch.Tensor):
         raise be.DpxError(f"tv_denoise: expected a torch.Tensor, got {type(v)}")
     if v.is_complex() or v.dtype != torch.float32:
         raise be.DpxError(f"tv_denoise: expected a real float32 volume, got {v.dtype}")
-    if torch.is_grad_enabled() and (v.requires_grad or (isinstance(lam, torch.Tensor) and lam.requires_grad)):
-        raise NotImplementedError("tv_denoise is forward-only: it has no backward kernel (the reference differentiates through its "
-                                  "TV steps); call it under torch.no_grad()")
+    needs_grad = torch.is_grad_enabled() and (v.requires_grad or (isinstance(lam, torch.Tensor) and lam.requires_grad))
+    if needs_grad and not differentiable:
+        raise NotImplementedError("tv_denoise is forward-only unless asked: pass differentiable=True (TVDenoiser(differentiable=True)) for the "
+                                  "backward kernel, which records (iters - 1) bytes per voxel in the forward pass, or call it under torch.no_grad()")
     N, D0, D1, D2 = _shape4(v)
     if min(N, D0, D1, D2) < 1:
         raise be.DpxError(f"tv_denoise: empty volume {tuple(v.shape)}")
@@ -1197,7 +1258,10 @@ def tv_denoise(v, lam, iters=5, axes=(1, 2)):
     if host_lam is not None and bool((torch.as_tensor(host_lam) < 0).any()):
         raise be.DpxError("tv_denoise: lam must be >= 0")
     v = require(v.contiguous(), what="tv_denoise input")
+    lam_in = lam
     lam = as_batch_vec(lam, N, v.device)            # (held until the call returns)
+    if needs_grad:
+        return _TVDenoiseFn.apply(v, lam_in if isinstance(lam_in, torch.Tensor) else None, lam, int(iters), mask)
     L = be.lib()
     ws = workspace("tv", L.query("dpx_tv_ws_bytes", N, D0, D1, D2, mask, int(iters)), v.device)
     out = torch.empty_like(v)

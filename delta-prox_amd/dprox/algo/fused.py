@@ -92,6 +92,11 @@ def _psi_prox_code(fn):
     return None
 
 
+def differentiable_tv_priors(psi_fns):
+    """the deep_prior terms whose denoiser is a TVDenoiser(differentiable=True): the one prior with a gradient that is opt-in"""
+    return [fn for fn in psi_fns if type(fn) is deep_prior and isinstance(fn.denoiser, TVDenoiser) and fn.denoiser.differentiable]
+
+
 def plan_fingerprint(solver):
     """everything mutable the pattern match of ``plan_admm`` reads, cheaply: the term lists (identity and type of every term), the
     terms' beta / unroll / clamp / x8 / sqrt, the denoiser's class AND identity, the linop at the root of each term (with the version of
@@ -494,6 +499,23 @@ class FusedADMM:
         finally:
             self._pending_chains = None
 
+    def _grad_request(self, x0, v, u, rhos, lams):
+        """(the Omega terms' offsets as autograd tensors, the trained PSFs, whether autograd asks this solve for any gradient)"""
+        s = self.solver
+        raw_offs = [self._offset_autograd(fn, x0) for fn in s.omega_fns]
+        trained_psfs = [cv.psf for cv in map(_omega_conv, s.omega_fns)
+                        if isinstance(cv, conv_doe) and cv.circular and isinstance(cv.psf, torch.Tensor) and cv.psf.requires_grad]
+        return raw_offs, trained_psfs, autodiff.needs_grad(x0, rhos, lams, raw_offs, list(v) + list(u) + trained_psfs)
+
+    def differentiates_tv_prior(self, state, rhos, lams):
+        """True when the problem has a TVDenoiser(differentiable=True) prior and autograd asks this solve for a gradient: such a solve runs
+        the unrolled mode of ``run`` -- every stage an autograd node, the prior's prox ops.tv_denoise's own Function (the recording forward
+        and dpx_tv_backward) -- never the no-gradient stages"""
+        if not differentiable_tv_priors(self.solver.psi_fns):
+            return False
+        x0, v, u = state
+        return self._grad_request(x0, v, u, rhos, lams)[2]
+
     def _run(self, state, rhos, lams, max_iter, pbar=False, callback=None, dual=True, vxu=False):
         """``dual=False``: half-quadratic splitting (hqs.py:4-20) = the same three stages with the dual variables pinned to
         zero -- state (x, [z_i]); the z-stage's ``u_out`` goes to a scratch buffer and is never read.
@@ -517,10 +539,11 @@ class FusedADMM:
             materialize_state(s, state)
             return state
 
-        raw_offs = [self._offset_autograd(fn, x0) for fn in s.omega_fns]
-        trained_psfs = [cv.psf for cv in map(_omega_conv, s.omega_fns)
-                        if isinstance(cv, conv_doe) and cv.circular and isinstance(cv.psf, torch.Tensor) and cv.psf.requires_grad]
-        want_grad = dual and not vxu and autodiff.needs_grad(x0, rhos, lams, raw_offs, list(v) + list(u) + trained_psfs)
+        raw_offs, trained_psfs, want_grad = self._grad_request(x0, v, u, rhos, lams)
+        want_grad = dual and not vxu and want_grad
+        # a TVDenoiser(differentiable=True) prior whose gradient is asked for never meets the no-gradient stages below (they would run its
+        # forward kernel where autograd cannot see it): ADMM.iters has selected the unrolled mode for it and says so in last_path
+        assert not (want_grad and differentiable_tv_priors(psi)) or s.last_path == "unrolled", s.last_path
         # (the differentiable path builds its own schedule tables as autograd nodes, autodiff.run: none are made here for it)
         rho_tab = None if want_grad else schedule_table(rhos, T, B, dev)
         _tr("rho table")

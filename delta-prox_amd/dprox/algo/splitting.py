@@ -53,7 +53,7 @@ class ADMM(Algorithm):
         self.least_square = get_least_square_solver(psi_fns, omega_fns, try_diagonalize, try_freq_diagonalize,
                                                     linear_solve_config)
         self.use_fused = True
-        self.last_path = None           # "fused" | "generic": which engine ran the last solve
+        self.last_path = None           # "fused" | "fused-cg" | "unrolled" | "generic": which engine ran the last solve
 
     def initialize(self, x0, v=None):
         x = x0
@@ -92,7 +92,10 @@ class ADMM(Algorithm):
     def iters(self, state, rhos, lams, max_iter, pbar=False, callback=None):
         plan = self._plan_for(state[0]) if (self.use_fused and type(self) is ADMM) else None
         if plan is not None:
-            self.last_path = "fused"
+            # A TVDenoiser(differentiable=True) prior under autograd is selected explicitly: "unrolled" -- the plan's stage-by-stage mode,
+            # every stage an autograd node, so that autograd sees the prior's own op (ops.tv_denoise's recording forward and backward
+            # kernel); "fused" is everything else the plan runs, the no-gradient stages among it.
+            self.last_path = "unrolled" if plan.differentiates_tv_prior(state, rhos, lams) else "fused"
             return plan.run(state, rhos, lams, max_iter, pbar, callback)
         fused.materialize_state(self, state)                   # (every other path reads the split variables)
         if self.use_fused and type(self) in (ADMM, LinearizedADMM):

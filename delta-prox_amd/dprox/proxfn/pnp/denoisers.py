@@ -60,14 +60,19 @@ class TVDenoiser(Denoiser):
     ``dims`` -- a tuple out of NCHW dims {1, 2, 3} -- selects the differenced axes itself (``dims=(2, 3)`` is the per-plane spatial TV
     of RGB / gray images) and overrides ``use_3dtv``; batches of N > 1 images with a per-image ``sigma`` ([N] or 0-d: the reference
     raises on N > 1); a differenced axis of length 1 contributes no differences but still counts in the mean over the axes (the
-    reference returns an empty tensor).  ``sigma`` must be >= 0; ``sigma = 0`` returns the input bit for bit.  The denoiser is
-    forward-only: a call that autograd would have to differentiate raises NotImplementedError (the reference does differentiate
-    through its TV steps; there is no backward kernel here yet)."""
+    reference returns an empty tensor).  ``sigma`` must be >= 0; ``sigma = 0`` returns the input bit for bit.
 
-    def __init__(self, iter_num=5, use_3dtv=False, dims=None):
+    The gradient is opt-in.  By default the denoiser is forward-only: a call that autograd would have to differentiate raises
+    NotImplementedError.  ``differentiable=True`` differentiates through the TV steps as the reference does (``dpx_tv_denoise_rec`` /
+    ``dpx_tv_backward``: gradients to the input and to ``sigma``, so a per-step ``sigma`` schedule of an unrolled solver can be
+    trained); the forward pass then records the clip state of every dual update, ``iter_num - 1`` bytes per voxel kept until the
+    backward pass -- the price the flag stands for.  A call that needs no gradient runs the plain forward either way."""
+
+    def __init__(self, iter_num=5, use_3dtv=False, dims=None, differentiable=False):
         super().__init__()
         self.iter_num = int(iter_num)
         self.use_3dtv = bool(use_3dtv)
+        self.differentiable = bool(differentiable)
         if dims is None:
             dims = (1, 2, 3) if self.use_3dtv else (1, 2)
         ops._tv_axes_mask(dims)                          # (raises on anything but a set of NCHW dims out of 1, 2, 3)
@@ -75,10 +80,10 @@ class TVDenoiser(Denoiser):
 
     def denoise(self, input, sigma):
         """input: [N, C, H, W]; sigma: 0-d or [N]"""
-        return ops.tv_denoise(input, sigma, self.iter_num, self.dims)
+        return ops.tv_denoise(input, sigma, self.iter_num, self.dims, differentiable=self.differentiable)
 
     def extra_repr(self):
-        return f"iter_num={self.iter_num}, dims={self.dims}"
+        return f"iter_num={self.iter_num}, dims={self.dims}" + (", differentiable=True" if self.differentiable else "")
 
 
 class RefKeyed(nn.Module):

@@ -16,9 +16,10 @@ CACHE_DIR = os.path.join(os.path.expanduser("~"), ".cache", "dprox")
 
 def get_denoiser(type):
     """pretrained weights are read from the reference's cache layout (~/.cache/dprox/pnp_denoisers/*.pth);
-    nothing is downloaded.  "tv" / "tv3d" (TVDenoiser(5, False) / TVDenoiser(5, True)) have no weights and need no file."""
-    if type in ("tv", "tv3d"):
-        return TVDenoiser(5, type == "tv3d")
+    nothing is downloaded.  "tv" / "tv3d" (TVDenoiser(5, False) / TVDenoiser(5, True)) have no weights and need no file;
+    "tv_diff" / "tv3d_diff" are the same with differentiable=True (the gradient is opt-in: TVDenoiser's docstring)."""
+    if type in ("tv", "tv3d", "tv_diff", "tv3d_diff"):
+        return TVDenoiser(5, type.startswith("tv3d"), differentiable=type.endswith("_diff"))
     table = {"ffdnet": ("ffdnet_gray.pth", FFDNetDenoiser), "ffdnet_color": ("ffdnet_color.pth", FFDNetColorDenoiser),
              "drunet": ("drunet_gray.pth", lambda p: DRUNetDenoiser(1, p)), "drunet_color": ("drunet_color.pth", lambda p: DRUNetDenoiser(3, p)),
              "ircnn": ("ircnn_gray.pth", lambda p: IRCNNDenoiser(1, p)), "unet": ("unet-nm.pt", UNetDenoiser)}

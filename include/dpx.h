@@ -109,6 +109,7 @@ int dpx_timing_report(char* buf, size_t cap);
  *                        of fewer than 8 planes of 1024-wide rows; bit-identical across band counts)
  *   tv_steps             dpx_tv_denoise: at most this many TV steps per launch on one LDS tile (0 = the       DPX_TV_STEPS
  *                        plan's choice, dpx_tv_plan; 1 = the one-step form); bit-identical for every value
+ *                        (dpx_tv_denoise_rec and dpx_tv_backward run the same plan: their out and gy likewise)
  */
 int dpx_tune_count(void);
 const char* dpx_tune_name(int i);                       /* NULL beyond dpx_tune_count() */
@@ -780,6 +781,24 @@ size_t dpx_tv_ws_bytes(int N, int D0, int D1, int D2, int axes, int iters);
 int dpx_tv_plan(int D0, int D1, int D2, int axes, int iters, int* out6);
 int dpx_tv_denoise(const float* y, float* out, const float* lam, int N, int D0, int D1, int D2, int axes, int iters, void* ws,
                    dpx_stream_t stream);
+/* The gradient of dpx_tv_denoise.  TV is piecewise linear: given the clip state of every dual update (below -lam_n / 2, inside -- equality
+ * included, as the backward of torch.clamp with tensor bounds counts it --, above) the reverse sweep is linear in the cotangent and needs
+ * neither y nor lam.
+ *   dpx_tv_denoise_rec  dpx_tv_denoise (the same `ws`, the same bits in `out`) that also records the states: one byte per voxel and step
+ *                       t = 1 .. iters - 1 (two bits per active axis), codes[iters - 1][N][D0 D1 D2], dpx_tv_codes_bytes long.
+ *   dpx_tv_backward     gy[N][D0][D1][D2] = (d out / d y)^T g and, unless glam is null, glam[N] = d <g, out> / d lam_n.  The forward's
+ *                       tiles run backwards (csrc/dpx_tv.hip: k_tv_bwd): up to S reverse steps per launch, iters > S a chain over
+ *                       hand-over buffers in `ws` (dpx_tv_bwd_ws_bytes: also the reduction's tickets and sums; ws may be null for one
+ *                       launch without glam).  gy is bit-identical for every S and tile; glam is summed in float64 in a fixed order, the
+ *                       same bits from run to run.  gy must not be g.  iters = 1: no states (codes may be null), gy = g, glam = 0.
+ *   dpx_tv_bwd_plan     as dpx_tv_plan, for dpx_tv_backward (the forward's S, launches and tile; its own LDS bytes).                 */
+size_t dpx_tv_codes_bytes(int N, int D0, int D1, int D2, int axes, int iters);
+int dpx_tv_denoise_rec(const float* y, float* out, const float* lam, unsigned char* codes, int N, int D0, int D1, int D2, int axes,
+                       int iters, void* ws, dpx_stream_t stream);
+size_t dpx_tv_bwd_ws_bytes(int N, int D0, int D1, int D2, int axes, int iters);
+int dpx_tv_bwd_plan(int D0, int D1, int D2, int axes, int iters, int* out6);
+int dpx_tv_backward(const float* g, const unsigned char* codes, float* gy, float* glam, int N, int D0, int D1, int D2, int axes, int iters,
+                    void* ws, dpx_stream_t stream);
 
 #ifdef __cplusplus
 }
