@@ -205,6 +205,8 @@ const KnobDef kKnobs[TUNE_COUNT] = {
     {"cg_event_wait", "DPX_CG_EVENT_WAIT", 0, nullptr},
     {"pnp_cg_no_fold", "DPX_PNP_CG_NO_FOLD", 0, nullptr},
     {"tv_steps", "DPX_TV_STEPS", 0, nullptr},
+    {"lp_lanes", "DPX_LP_LANES", 0, nullptr},
+    {"lp_split_direction", "DPX_LP_SPLIT_DIRECTION", 0, nullptr},
 };
 std::atomic<int> g_knob[TUNE_COUNT];
 std::once_flag g_knob_once;

@@ -241,6 +241,15 @@ SIGNATURES = {
     "dpx_minres_lanczos": (c_int, [c_void_p, c_void_p, c_double, c_double, c_int, c_void_p, c_int, c_int, c_long, c_int, c_int, c_void_p, c_void_p]),
     "dpx_minres_beta": (c_int, [c_void_p, c_void_p, c_double, c_void_p, c_int, c_int, c_long, c_int, c_int, c_void_p, c_void_p]),
     "dpx_minres_update": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_long, c_int, c_int, c_void_p, c_void_p]),
+    "dpx_lp_state_bytes": (c_size_t, []),
+    "dpx_lp_ws_bytes": (c_size_t, [c_long, c_long]),
+    "dpx_lp_lanes": (c_int, [c_long, c_long]),
+    "dpx_lp_spmv": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_long, c_void_p]),
+    "dpx_lp_spmv_chain": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_long, c_int, c_void_p]),
+    "dpx_lp_pcg_start": (c_int, [c_void_p, c_long, c_long, c_long, c_double, c_double, c_double, c_void_p]),
+    "dpx_lp_pcg_iters": (c_int, [c_void_p, c_long, c_long, c_long, c_double, c_double, c_long, c_int, c_void_p]),
+    "dpx_lp_tail": (c_int, [c_void_p, c_long, c_long, c_long, c_double, c_double, c_void_p]),
+    "dpx_lp_eval": (c_int, [c_void_p, c_long, c_long, c_long, c_double, c_double, c_void_p]),
 }
 
 

@@ -573,6 +573,92 @@ class MinresControl:
                       ptr(self.ws), be.stream())
 
 
+class LpControl:
+    """device-resident state of one LPSolverADMM.solve (dpx_lp_*, csrc/dpx_lp.hip): the two CSR copies of the scaled constraint
+    matrix, the ADMM iterates x, xt, z, y, the PCG vectors and the state block; the host only issues launches and reads the state
+    block where the reference synchronises too.  Everything is float64; the inputs are NumPy arrays (``csr`` = (indptr, indices,
+    data), validated by the caller).  ``fields()`` names the state's parts; ``launches`` counts the kernels issued."""
+    TABLE = ("a_ptr", "a_idx", "a_val", "at_ptr", "at_idx", "at_val", "x", "xt", "z", "y", "t", "c", "acn", "right", "r", "yv", "p", "Ap",
+             "lb", "ub", "d", "e", "state", "ws")
+    MAX_INNER = 1000                       # the reference's pcg(..., max_iters=int(1e3))
+
+    def __init__(self, csr_a, csr_at, m, n, c, acn, lb, ub, d, e, device):
+        self.m, self.n, self.nnz = int(m), int(n), int(len(csr_a[2]))
+        dev = torch.device(device)
+        put = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a, dtype=dt)).to(dev)
+        b = {}
+        for tag, (indptr, indices, data), rows in (("a", csr_a, self.m), ("at", csr_at, self.n)):
+            if len(indptr) != rows + 1 or len(indices) != self.nnz or len(data) != self.nnz or self.nnz > 2 ** 31 - 65:
+                raise be.DpxError(f"lp: CSR arrays of lengths {len(indptr)}, {len(indices)}, {len(data)} for {rows} rows and {self.nnz} entries")
+            b[f"{tag}_ptr"], b[f"{tag}_idx"], b[f"{tag}_val"] = put(indptr, np.int32), put(indices, np.int32), put(data, np.float64)
+        for name, a, length in (("c", c, n), ("acn", acn, n), ("d", d, n), ("lb", lb, m), ("ub", ub, m), ("e", e, m)):
+            if np.shape(a) != (length,):
+                raise be.DpxError(f"lp: {name} of shape {np.shape(a)} (expected ({length},))")
+            b[name] = put(a, np.float64)
+        for name, length in (("x", n), ("xt", n), ("right", n), ("r", n), ("yv", n), ("p", 2 * n), ("Ap", n), ("z", m), ("y", m), ("t", m)):
+            b[name] = torch.zeros(length, dtype=torch.float64, device=dev)
+        L = be.lib()
+        b["state"] = _bytes(L.query("dpx_lp_state_bytes"), dev, zero=True)
+        # (the reductions' ticket lives at the head of the workspace and must start from zero: not the shared scratch of workspace())
+        b["ws"] = _bytes(L.query("dpx_lp_ws_bytes", self.m, self.n), dev, zero=True)
+        for t in b.values():
+            require(t, dtype=None, what="lp buffer")
+        self.buf = b
+        self.tab = (c_void_p * len(self.TABLE))(*[b[k].data_ptr() for k in self.TABLE])
+        self._dims = (self.m, self.n, self.nnz)
+        self.words = b["state"][14 * 8:17 * 8].view(torch.int64)          # done, inner, ops
+        self.launches = 0
+
+    def __getattr__(self, name):
+        buf = self.__dict__.get("buf", {})
+        if name in buf:
+            return buf[name]
+        raise AttributeError(name)
+
+    def fields(self):
+        """views into the state block: ry, a, beta, rtol, pAp, rmax (float64 [1]), eval (float64 [8]: objval, r_norm, s_norm, |A x|,
+        |z|, |AT y|, |c|, |z - clip(z)|), done, inner, ops (int64 [1])"""
+        f64 = self.buf["state"][:14 * 8].view(torch.float64)
+        out = {k: f64[i:i + 1] for i, k in enumerate(("ry", "a", "beta", "rtol", "pAp", "rmax"))}
+        out["eval"] = f64[6:14]
+        out.update({k: self.words[i:i + 1] for i, k in enumerate(("done", "inner", "ops"))})
+        return out
+
+    def lanes(self):
+        """(lanes per row of A, of AT) the kernels use now"""
+        L = be.lib()
+        return L.query("dpx_lp_lanes", self.m, self.nnz), L.query("dpx_lp_lanes", self.n, self.nnz)
+
+    def spmv(self, which, v, reps=1):
+        """A v (``which`` = "a", v [n]) or AT v ("at", v [m]): the plain row product (``reps``: issued that often from one call)"""
+        rows, cols = (self.m, self.n) if which == "a" else (self.n, self.m)
+        require(v, dtype=torch.float64, what="lp vector")
+        if tuple(v.shape) != (cols,):
+            raise be.DpxError(f"lp: a vector of shape {tuple(v.shape)} for a matrix with {cols} columns")
+        out = torch.empty(rows, dtype=torch.float64, device=v.device)
+        b = self.buf
+        be.lib().call("dpx_lp_spmv_chain", ptr(out), ptr(b[f"{which}_ptr"]), ptr(b[f"{which}_idx"]), ptr(b[f"{which}_val"]), ptr(v), rows, self.nnz,
+                      int(reps), be.stream())
+        self.launches += int(reps)
+        return out
+
+    def pcg_start(self, rho, sigma, rtol):
+        be.lib().call("dpx_lp_pcg_start", self.tab, *self._dims, c_double(rho), c_double(sigma), c_double(rtol), be.stream())
+        self.launches += 1
+
+    def pcg_iters(self, rho, sigma, iters=1):
+        be.lib().call("dpx_lp_pcg_iters", self.tab, *self._dims, c_double(rho), c_double(sigma), self.MAX_INNER, int(iters), be.stream())
+        self.launches += int(iters) * (4 if be.tune_get("lp_split_direction") else 3)
+
+    def tail(self, alpha, rho):
+        be.lib().call("dpx_lp_tail", self.tab, *self._dims, c_double(alpha), c_double(rho), be.stream())
+        self.launches += 1
+
+    def eval(self, gamma_c, gamma_b):
+        be.lib().call("dpx_lp_eval", self.tab, *self._dims, c_double(gamma_c), c_double(gamma_b), be.stream())
+        self.launches += 2
+
+
 def prox(kind, v, lam, alpha=1.0, off=None, out=None):
     require(v, what="prox input")
     B = int(v.shape[0])

@@ -9,7 +9,9 @@ import torch.nn as nn
 
 from .. import _backend as be
 from ..linalg import LinearSolveConfig
+from ..linop.constaints import equality, less, matmul
 from ..proxfn import ProxFn
+from . import lp
 from .deq import DEQSolver
 from .driver import Algorithm
 from .gradient import ProximalGradientDescent
@@ -146,9 +148,52 @@ def specialize(solver: Algorithm, method: str = "unroll", device: Union[str, tor
     return solver.to(_resolve_device(device))
 
 
+class LinearProgram:
+    """``Problem(c @ x, [A_ub @ x <= b_ub, A_eq @ x == b_eq])`` (the reference's algo/problem.py:LPProblem, with its settings):
+    ``solve()`` returns the solution vector x, float64 on the device.  Two differences from the reference, on purpose: it returns
+    ``x.min()``, a debugging leftover, and it always trains rho, sigma and alpha first (``optimize_params``), which is not built
+    here -- ``adapt_params`` therefore defaults to False and True raises."""
+
+    def __init__(self, objective, constraints, max_iters=20000, abstol=1e-3, reltol=1e-6, rho=1e-1):
+        self.objective, self.constraints = objective, constraints
+        found = {}
+        for con in constraints:
+            if isinstance(con, (equality, less)):
+                if type(con) in found:
+                    raise ValueError(f"Problem: two `{type(con).__name__}` constraints (a linear program takes one of each)")
+                found[type(con)] = con
+        if len(constraints) != 2 or len(found) != 2:
+            raise ValueError("Problem: a linear program takes exactly one `A_ub @ x <= b_ub` and one `A_eq @ x == b_eq`")
+        for con in (objective, found[less].left, found[equality].left):
+            if con.var is not objective.var:
+                raise ValueError("Problem: the objective and the constraints of a linear program are in one variable")
+        self.args = (objective.A, found[less].left.A, found[less].right, found[equality].left.A, found[equality].right)
+        self.solver = lp.LPSolverADMM(rho=rho, problem_scale=None, abstol=abstol, reltol=reltol, max_iters=max_iters, verbose=False)
+        self.prob = None
+
+    def optimize_params(self):
+        self.solver.optimize_params()
+
+    def solve(self, method="admm", device="cuda", adapt_params=False):
+        if method != "admm":
+            raise NotImplementedError(f"Problem.solve: a linear program is solved by ADMM (method={method!r})")
+        if adapt_params:
+            self.optimize_params()
+        self.prob = lp.LPProblem(*self.args, device=_resolve_device(device))
+        self.solver.eval()
+        x, self.history, self.results = self.solver.solve(self.prob, residual_balance=True)
+        return x.reshape(-1)
+
+
 class Problem:
     def __init__(self, prox_fns: Union[ProxFn, List[ProxFn]], constraints=[], absorb=True, merge=True,
                  try_diagonalize=True, try_freq_diagonalize=True, linear_solve_config=LinearSolveConfig()):
+        self.prob = None
+        if isinstance(prox_fns, matmul):
+            self.prox_fns = prox_fns
+            self.prob = LinearProgram(prox_fns, constraints)
+            self.solver = self.prob.solver
+            return
         if isinstance(prox_fns, ProxFn):
             prox_fns = [prox_fns]
         self.prox_fns = prox_fns
@@ -162,6 +207,8 @@ class Problem:
         return self.prox_fns
 
     def solve(self, method="admm", device="cuda", **kwargs):
+        if self.prob is not None:
+            return self.prob.solve(method=method, device=device, **kwargs)
         args = self.solver_args if method != "pgd" else {}
         self.solver = compile(self.prox_fns, method=method, device=device, **args)
         return self.solver.solve(**kwargs)

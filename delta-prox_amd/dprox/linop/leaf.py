@@ -38,6 +38,11 @@ class Variable(LinOp):
     def get_diag(self, ref, freq=False):
         return torch.ones(ref.shape)
 
+    def __rmatmul__(self, other):
+        """``other @ x``: the linear-program pieces ``c @ x`` and ``A @ x`` (LinOp.__array_priority__ makes ``ndarray @ x`` land here)"""
+        from .constaints import matmul
+        return matmul(self, other)
+
     @property
     def variables(self):
         return [self]

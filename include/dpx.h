@@ -110,6 +110,10 @@ int dpx_timing_report(char* buf, size_t cap);
  *   tv_steps             dpx_tv_denoise: at most this many TV steps per launch on one LDS tile (0 = the       DPX_TV_STEPS
  *                        plan's choice, dpx_tv_plan; 1 = the one-step form); bit-identical for every value
  *                        (dpx_tv_denoise_rec and dpx_tv_backward run the same plan: their out and gy likewise)
+ *   lp_lanes             dpx_lp_*: lanes that walk one CSR row (a power of two, 1 .. 64; 0 = the library's      DPX_LP_LANES
+ *                        rule: the smallest power of two that covers the mean row length)
+ *   lp_split_direction   dpx_lp_pcg_iters: 1 = the direction update p = -y + beta p as a launch of its own     DPX_LP_SPLIT_DIRECTION
+ *                        instead of folded into the next product's gather (bit-identical)
  */
 int dpx_tune_count(void);
 const char* dpx_tune_name(int i);                       /* NULL beyond dpx_tune_count() */
@@ -799,6 +803,54 @@ size_t dpx_tv_bwd_ws_bytes(int N, int D0, int D1, int D2, int axes, int iters);
 int dpx_tv_bwd_plan(int D0, int D1, int D2, int axes, int iters, int* out6);
 int dpx_tv_backward(const float* g, const unsigned char* codes, float* gy, float* glam, int N, int D0, int D1, int D2, int axes, int iters,
                     void* ws, dpx_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------ */
+/* LP solver (sparse float64 ADMM with a device-controlled PCG)                                */
+/* ------------------------------------------------------------------------------------------ */
+/* LPSolverADMM.solve -- algo/lp/solvers.py:132-336 with the PCG of linalg/solve/solver_cg.py:172-233 as its x-update.  Everything is
+ * float64.  Abar (m x n, m = m_ub + m_eq + n: the last n rows are the scaled identity) is given twice, as CSR of Abar and CSR of its
+ * transpose (int32 offsets and indices, nnz <= 2^31 - 65 -- the row loops step an offset by up to 64 past a row's end -- and m >= n,
+ * both refused otherwise; the caller has validated the arrays: monotone offsets, indices in range, no empty row).  The device buffers of a solve travel as one table of DPX_LP_TAB_COUNT pointers (a host array), none null:
+ *   A_PTR [m + 1], A_IDX, A_VAL [nnz]      CSR of Abar            AT_PTR [n + 1], AT_IDX, AT_VAL [nnz]     CSR of Abar^T
+ *   X, XT [n]   x and x-tilde                Z, Y [m]   z and the dual y             T [m]   Abar xt / Abar p
+ *   C [n]       gamma_c d c                  ACN [n]    column 2-norms of Abar      RIGHT, R, YV, AP [n]   PCG vectors (YV = Minv r)
+ *   P [2][n]    the PCG direction, double-buffered: inner iteration i uses slot i & 1
+ *   LB, UB [m]  scaled bounds (+-inf kept)   D [n], E [m]   the equilibration's scalings
+ *   STATE       dpx_lp_state_bytes: doubles ry, a, beta, rtol, <p, Ap>, max|r|, eval[8] = objval, r_norm, s_norm, |Abar x / e / gamma_b|,
+ *               |z / e / gamma_b|, |Abar^T y / d / gamma_c|, |c / d / gamma_c|, |z - clip(z)| (all infinity norms), then int64 done,
+ *               inner (iterations of the current PCG), ops (operator applications since the block was zeroed)
+ *   WS          dpx_lp_ws_bytes: zero-filled at its first use; every call leaves its head zero again
+ * One outer iteration: dpx_lp_pcg_start, dpx_lp_pcg_iters until STATE.done, dpx_lp_tail.  T must hold Abar xt at the start: zeros
+ * with xt = 0, afterwards dpx_lp_tail has left it.
+ *   dpx_lp_pcg_start  right = sigma x - c + Abar^T(rho z - y), r = Abar^T(rho T) + sigma xt - right, yv = r / M, p = -yv,
+ *                     ry = <r, yv>; rtol is stored, done = inner = 0, ops += 1.  M = sigma + rho ACN^2.
+ *   dpx_lp_pcg_iters  `iters` inner iterations (three launches each; four with knob lp_split_direction): T = Abar p,
+ *                     AP = Abar^T(rho T) + sigma p, a = ry / <p, AP>, xt += a p, r += a AP, yv = r / M, beta = <r, yv> / ry,
+ *                     p = -yv + beta p, inner += 1, ops += 1, done = max|r| < rtol or inner == max_inner (a NaN in r makes max|r| NaN and
+ *                     the test false, as in the reference).  Iterations issued after done is set change nothing.
+ *   dpx_lp_tail       T = Abar xt, x = alpha xt + (1 - alpha) x, zt = alpha T + (1 - alpha) z, z = clip(zt + y / rho, lb, ub),
+ *                     y += rho (zt - z)
+ *   dpx_lp_eval       eval[8] of STATE from x, z, y
+ *   dpx_lp_spmv       out[rows] = M v for one CSR matrix (the row product the others are built around)
+ *   dpx_lp_spmv_chain the same product `reps` times back to back (for timing the kernel without one host call per launch)
+ *   dpx_lp_lanes      lanes per row the kernels use for `rows` rows with nnz entries (a power of two, 1 .. 64; knob lp_lanes)
+ * Reductions add per-workgroup partials in a fixed order: no floating-point atomics, two runs give the same bits.               */
+enum {
+  DPX_LP_A_PTR = 0, DPX_LP_A_IDX, DPX_LP_A_VAL, DPX_LP_AT_PTR, DPX_LP_AT_IDX, DPX_LP_AT_VAL, DPX_LP_X, DPX_LP_XT, DPX_LP_Z, DPX_LP_Y, DPX_LP_T,
+  DPX_LP_C, DPX_LP_ACN, DPX_LP_RIGHT, DPX_LP_R, DPX_LP_YV, DPX_LP_P, DPX_LP_AP, DPX_LP_LB, DPX_LP_UB, DPX_LP_D, DPX_LP_E, DPX_LP_STATE,
+  DPX_LP_WS, DPX_LP_TAB_COUNT
+};
+size_t dpx_lp_state_bytes(void);
+size_t dpx_lp_ws_bytes(long m, long n);
+int dpx_lp_lanes(long rows, long nnz);
+int dpx_lp_spmv(void* out, const int* indptr, const int* indices, const void* data, const void* v, long rows, long nnz, dpx_stream_t stream);
+int dpx_lp_spmv_chain(void* out, const int* indptr, const int* indices, const void* data, const void* v, long rows, long nnz, int reps,
+                      dpx_stream_t stream);
+int dpx_lp_pcg_start(const void* const* tab, long m, long n, long nnz, double rho, double sigma, double rtol, dpx_stream_t stream);
+int dpx_lp_pcg_iters(const void* const* tab, long m, long n, long nnz, double rho, double sigma, long max_inner, int iters,
+                     dpx_stream_t stream);
+int dpx_lp_tail(const void* const* tab, long m, long n, long nnz, double alpha, double rho, dpx_stream_t stream);
+int dpx_lp_eval(const void* const* tab, long m, long n, long nnz, double gamma_c, double gamma_b, dpx_stream_t stream);
 
 #ifdef __cplusplus
 }
