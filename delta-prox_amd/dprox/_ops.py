@@ -1353,3 +1353,124 @@ def tv_denoise(v, lam, iters=5, axes=(1, 2), differentiable=False):
     out = torch.empty_like(v)
     L.call("dpx_tv_denoise", ptr(v), ptr(out), ptr(lam), N, D0, D1, D2, mask, int(iters), ptr(ws), be.stream())
     return out
+
+
+# ----------------------------------------------------------------------------------------------
+# compress_sensing: the coded-aperture x-update (dpx_cs_xupdate / dpx_cs_backward, csrc/dpx_cs.hip)
+# ----------------------------------------------------------------------------------------------
+CS_MAX_IN = 4            # right-hand sides one dpx_cs_xupdate launch adds up
+
+
+def _cs_operands(shape, y, mask):
+    """(y as [Ny, H, W], the mask as [Nm, C, H, W]) for an [N, C, H, W] iterate (Ny, Nm: 1 = shared by the batch, or N): checked,
+    contiguous fp32"""
+    N, C, H, W = shape
+    for t, what in ((mask, "mask"), (y, "y")):
+        if not isinstance(t, torch.Tensor):
+            raise be.DpxError(f"cs_xupdate: {what}: expected a torch.Tensor, got {type(t)}")
+        if t.is_complex() or t.dtype != torch.float32:
+            raise be.DpxError(f"cs_xupdate: {what}: expected real float32, got {t.dtype}")
+    ms = tuple(mask.shape)
+    if ms == (C, H, W):
+        ms = (1,) + ms
+    if ms not in ((1, C, H, W), (N, C, H, W)):
+        raise be.DpxError(f"cs_xupdate: mask {tuple(mask.shape)} does not broadcast to the iterate {tuple(shape)} ([C,H,W], [1,C,H,W] or [N,C,H,W])")
+    ys = tuple(y.shape)
+    if ys not in ((H, W), (1, H, W), (N, H, W), (1, 1, H, W), (N, 1, H, W)):
+        raise be.DpxError(f"cs_xupdate: y {ys} does not broadcast to the iterate {tuple(shape)} ([N,1,H,W], [1,1,H,W], [N,H,W] or [H,W])")
+    Ny = 1 if len(ys) == 2 else ys[0]
+    y3, mask4 = y.detach().reshape(Ny, H, W).contiguous(), mask.detach().reshape(ms).contiguous()
+    return require(y3, what="cs_xupdate y"), require(mask4, what="cs_xupdate mask")
+
+
+def _cs_forward(bs, y3, mask4, lam_vec, num_psi):
+    """one dpx_cs_xupdate launch on checked operands; more than CS_MAX_IN right-hand sides: the leading ones are added up first"""
+    if len(bs) > CS_MAX_IN:
+        k = len(bs) - CS_MAX_IN + 1
+        bs = [lincomb([(1.0, t) for t in bs[:k]])] + list(bs[k:])
+    N, C, H, W = _shape4(bs[0])
+    x = torch.empty_like(bs[0])
+    pb = (c_void_p * len(bs))(*[t.data_ptr() for t in bs])
+    be.lib().call("dpx_cs_xupdate", pb, len(bs), ptr(y3), ptr(mask4), ptr(lam_vec), int(num_psi), ptr(x), N, C, H, W, int(mask4.shape[0]),
+                  int(y3.shape[0]), be.stream())
+    return x
+
+
+def cs_backward(g, v, y3, mask4, lam_vec, num_psi, want=(True, True, True, True)):
+    """(gv, gy, glam [N], gmask) of dpx_cs_backward for the cotangent g [N, C, H, W]; an entry of `want` that is False is not computed
+    (None): gy and gmask come in the shapes of y3 [Ny, H, W] and mask4 [Nm, C, H, W], summed over the batch where those are shared"""
+    g = require(g.contiguous(), what="cs_backward cotangent")
+    N, C, H, W = _shape4(g)
+    L = be.lib()
+    gv = torch.empty_like(g) if want[0] else None
+    gy = torch.empty_like(y3) if want[1] else None
+    glam = torch.empty(N, dtype=torch.float32, device=g.device) if want[2] else None
+    gmask = torch.empty_like(mask4) if want[3] else None
+    ws = workspace("cs_bwd", L.query("dpx_cs_bwd_ws_bytes", N, C, H, W), g.device) if want[2] else None
+    L.call("dpx_cs_backward", ptr(g), ptr(v), ptr(y3), ptr(mask4), ptr(lam_vec), int(num_psi), ptr(gv), ptr(gy), ptr(glam), ptr(gmask), N, C, H, W,
+           int(mask4.shape[0]), int(y3.shape[0]), ptr(ws), be.stream())
+    return gv, gy, glam, gmask
+
+
+class _CSXUpdateFn(torch.autograd.Function):
+    """ops.cs_xupdate under autograd: the forward launch as it stands (its inputs are kept, nothing else), dpx_cs_backward recomputes from them"""
+
+    @staticmethod
+    def forward(ctx, y, mask, lam, y3, mask4, lam_vec, num_psi, *bs):
+        ctx.y3, ctx.mask4, ctx.lam_vec, ctx.num_psi, ctx.bs = y3, mask4, lam_vec, num_psi, [b.detach() for b in bs]
+        ctx.y_shape, ctx.mask_shape = tuple(y.shape), tuple(mask.shape)
+        ctx.lam_shape = tuple(lam.shape) if isinstance(lam, torch.Tensor) else None
+        ctx.lam_device = lam.device if isinstance(lam, torch.Tensor) else None
+        return _cs_forward(ctx.bs, y3, mask4, lam_vec, num_psi)
+
+    @staticmethod
+    def backward(ctx, g):
+        need = ctx.needs_input_grad
+        want = (any(need[7:]), need[0], need[2], need[1])
+        v = ctx.bs[0] if len(ctx.bs) == 1 else lincomb([(1.0, t) for t in ctx.bs])
+        gv, gy, glam, gmask = cs_backward(g, v, ctx.y3, ctx.mask4, ctx.lam_vec, ctx.num_psi, want)
+        if want[2]:
+            N = glam.shape[0]
+            n_lam = int(np.prod(ctx.lam_shape)) if ctx.lam_shape else 1
+            glam = (glam if n_lam == N else glam.sum()).reshape(ctx.lam_shape).to(ctx.lam_device)     # (one lam for N images: their sum)
+        gy = gy.reshape(ctx.y_shape) if want[1] else None
+        gmask = gmask.reshape(ctx.mask_shape) if want[3] else None
+        return (gy, gmask, glam, None, None, None, None) + tuple(gv if n else None for n in need[7:])
+
+
+def cs_xupdate(bs, y, mask, lam, num_psi):
+    """compress_sensing's closed-form x-update on the sum v of the [N, C, H, W] fp32 right-hand sides `bs` (ADMM hands over num_psi of
+    them; a prox call one, num_psi = 1), in one dpx_cs_xupdate launch that adds them up itself (more than four: the leading ones by
+    ops.lincomb first):
+
+        s = sum_c m_c v_c,  phi = sum_c m_c^2,  d = phi + num_psi lam,  r = (num_psi y - s) / d,  x_c = (v_c + m_c r) / num_psi
+
+    mask: real, any values, [C,H,W] / [1,C,H,W] / [N,C,H,W]; y: [N,1,H,W] / [1,1,H,W] / [N,H,W] / [H,W] (a leading 1 is shared by the
+    batch); lam: per-image (0-d / [N]), > 0 (checked where it is a host value; a device tensor is not read back); a new tensor.
+    Under autograd, where any of bs, y, lam, mask requires a gradient, the backward is dpx_cs_backward (every b receives the gradient to
+    v; lam's comes in lam's own shape); a call that needs no gradient saves nothing."""
+    bs = [bs] if isinstance(bs, torch.Tensor) else list(bs)
+    if not bs:
+        raise be.DpxError("cs_xupdate: nb = 0 right-hand sides (at least one)")
+    for b in bs:
+        if not isinstance(b, torch.Tensor):
+            raise be.DpxError(f"cs_xupdate: expected a torch.Tensor, got {type(b)}")
+        if b.is_complex() or b.dtype != torch.float32:
+            raise be.DpxError(f"cs_xupdate: expected real float32 right-hand sides, got {b.dtype}")
+        if b.shape != bs[0].shape:
+            raise be.DpxError(f"cs_xupdate: right-hand sides of shapes {tuple(bs[0].shape)} and {tuple(b.shape)}")
+    shape = _shape4(bs[0])
+    if min(shape) < 1:
+        raise be.DpxError(f"cs_xupdate: empty iterate {shape}")
+    if isinstance(num_psi, bool) or int(num_psi) != num_psi or num_psi < 1:
+        raise be.DpxError(f"cs_xupdate: num_psi {num_psi} (an integer >= 1)")
+    host_lam = lam if not isinstance(lam, torch.Tensor) else (lam.detach() if lam.device.type == "cpu" else None)
+    if host_lam is not None and bool((torch.as_tensor(host_lam) <= 0).any()):
+        raise be.DpxError("cs_xupdate: lam must be > 0")
+    y3, mask4 = _cs_operands(shape, y, mask)
+    needs_grad = torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in bs + [y, mask, lam])
+    bs = [require(b.contiguous(), what="cs_xupdate right-hand side") for b in bs]
+    lam_vec = as_batch_vec(lam, shape[0], bs[0].device)             # (held until the call returns)
+    if needs_grad:
+        return _CSXUpdateFn.apply(y, mask, lam if isinstance(lam, torch.Tensor) else None, y3, mask4, lam_vec, int(num_psi), *bs)
+    return _cs_forward([b.detach() for b in bs], y3, mask4, lam_vec, int(num_psi))

@@ -805,6 +805,30 @@ int dpx_tv_backward(const float* g, const unsigned char* codes, float* gy, float
                     void* ws, dpx_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------ */
+/* compress_sensing (coded-aperture data term of snapshot compressive imaging)                 */
+/* ------------------------------------------------------------------------------------------ */
+/* compress_sensing._prox -- proxfn/fast/cs.py:12-27 -- as ADMM's closed-form x-update.  Per image n and pixel (h, w), channels
+ * c = 0 .. C - 1, I = num_psi >= 1, lam = lam[n] > 0 (the caller's contract):
+ *   s = sum_c m_c v_c,   phi = sum_c m_c^2,   d = phi + I lam,   r = (I y - s) / d,   x_c = (v_c + m_c r) / I
+ * the solution of (A^T A + I lam) x = A^T y + lam v with A v = sum_c m_c v_c (csrc/dpx_cs.hip).  Contiguous fp32 buffers:
+ * v, x [N][C][H][W]; mask [mask_batch][C][H][W], any real values; y [y_batch][H][W]; mask_batch and y_batch are 1 (shared by the
+ * batch) or N; lam [N] on the device.
+ *   dpx_cs_xupdate       x from v = b[0] + .. + b[nb - 1] (a host array of 1 <= nb <= 4 device pointers, added in that order inside
+ *                        the kernel): one launch, nb C + C + 1 floats read and C written per pixel, no workspace.  x is none of b.
+ *   dpx_cs_backward      the gradient for the cotangent g [N][C][H][W], recomputed from v, y, mask, lam (the forward saves nothing):
+ *                        with t = sum_c m_c g_c and q = t / d,
+ *                          gv_c = (g_c - m_c q) / I,   gy = q,   glam[n] = -sum_{h,w} q r,   gmask_c = (g_c r - q (v_c + 2 m_c r)) / I
+ *                        gv [N][C][H][W] (every b[i] receives it); gy and gmask in the shapes of y and mask, summed over n where those
+ *                        are shared; glam [N].  Any of the four may be null.  The sums over n are formed by one thread in n order,
+ *                        glam by per-workgroup float64 sums added in a fixed order (`ws`, dpx_cs_bwd_ws_bytes; may be null when
+ *                        glam is): no floating-point atomics, the same bits from run to run.  One launch.                          */
+int dpx_cs_xupdate(const float* const* b, int nb, const float* y, const float* mask, const float* lam, int num_psi, float* x, int N, int C,
+                   int H, int W, int mask_batch, int y_batch, dpx_stream_t stream);
+size_t dpx_cs_bwd_ws_bytes(int N, int C, int H, int W);
+int dpx_cs_backward(const float* g, const float* v, const float* y, const float* mask, const float* lam, int num_psi, float* gv, float* gy,
+                    float* glam, float* gmask, int N, int C, int H, int W, int mask_batch, int y_batch, void* ws, dpx_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------ */
 /* LP solver (sparse float64 ADMM with a device-controlled PCG)                                */
 /* ------------------------------------------------------------------------------------------ */
 /* LPSolverADMM.solve -- algo/lp/solvers.py:132-336 with the PCG of linalg/solve/solver_cg.py:172-233 as its x-update.  Everything is
