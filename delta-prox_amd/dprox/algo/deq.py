@@ -228,7 +228,7 @@ class DEQSolver(nn.Module):
             n = len(s.psi_fns)
             with torch.no_grad():
                 x, v, u = s.initialize(x0)
-                s._fresh = None
+                fused.clear_fresh(s)
                 step = _FusedStep(s, plan, x0, rho.detach(), {fn: val.detach() for fn, val in lam.items()})
                 out = anderson_pieces(step, [x.contiguous()] + [t.contiguous() for t in v] + [t.contiguous() for t in u], threshold=f_thres, eps=self.eps)
             self.last_forward = out

@@ -21,6 +21,7 @@ op-by-op path on the same HIP primitives (never to PyTorch or the CPU).
 """
 import ctypes
 import os
+from types import SimpleNamespace
 
 import torch
 from tqdm import tqdm
@@ -140,6 +141,30 @@ def plan_admm(solver, state):
     return FusedADMM(solver, codes)
 
 
+def two_kernel_takes(codes, H, W):
+    """True when the two-kernel iteration takes a problem with these (linop, prox) codes on H x W planes: at least one term, closed-form
+    proxes only, a plane size / term set dpx_admm_iter_supported accepts (it reads the size and the codes, nothing else).  THE place that
+    asks: ``lazy_initial_state`` and ``FusedADMM.route`` go by this one answer, so a lazy state always meets an engine that seeds from x0."""
+    if not codes or any(pc == be.PROX_EXTERNAL for _, pc in codes):
+        return False
+    terms = (ops.Term * len(codes))()
+    for tm, (lc, pc) in zip(terms, codes):
+        tm.linop, tm.prox = lc, pc
+    return ops.iter_supported(H, W, terms, len(codes))
+
+
+def set_fresh(solver, x, v, u, lazy=False):
+    """the fresh-state marker, written here alone: (x, v, u) is what ``ADMM.initialize(x)`` returns and nobody has written to it since
+    (``fresh_state`` compares the tensors and their version counters); lazy: v and u are allocated but not computed"""
+    solver._fresh = (x, list(v), list(u), [t._version for t in [x, *v, *u]])
+    solver._fresh_lazy = lazy
+
+
+def clear_fresh(solver):
+    """no state counts as fresh (any more); _fresh_lazy says something about a marked state only and stays as it is"""
+    solver._fresh = None
+
+
 def lazy_initial_state(solver, x0, plan):
     """ADMM.solve's private initial state for problems the two-kernel iteration takes: (x0, [v_i], [u_i]) whose split variables are
     ALLOCATED but not computed -- v_i = K_i x0 and u_i = 0 are implied (``solver._fresh`` says so) and the fresh-state path never
@@ -149,28 +174,21 @@ def lazy_initial_state(solver, x0, plan):
     real thing for any path that does read the state.  None when the problem does not qualify."""
     if not (isinstance(x0, torch.Tensor) and x0.ndim == 4 and x0.dtype == torch.float32 and x0.is_contiguous()):
         return None
-    if plan is None or not plan.codes or any(pc == be.PROX_EXTERNAL for _, pc in plan.codes):
-        return None
-    B, C, H, W = x0.shape
-    early = ops.make_terms([dict(linop=lc, prox=pc, alpha=1.0, lam=None, v=x0, u=x0) for lc, pc in plan.codes])
-    if not ops.iter_supported(H, W, early, len(plan.codes)):
+    if plan is None or not two_kernel_takes(plan.codes, x0.shape[2], x0.shape[3]):
         return None
     n = len(plan.codes)
     v = [torch.empty_like(x0) for _ in range(n)]
     U = torch.empty((n,) + tuple(x0.shape), dtype=x0.dtype, device=x0.device)
     U[:, :, 0, 0, :].zero_()                                   # (row 0 of plane 0 of every IMAGE: sub-batch chains start at any of them; one
     u = list(U.unbind(0))                                      #  fill for all terms -- a training step of 1 ms counts its 4-us launches)
-    solver._fresh = (x0, v, u, [t._version for t in [x0] + v + u])
-    solver._fresh_lazy = True
+    set_fresh(solver, x0, v, u, lazy=True)
     return x0, v, u
 
 
 def materialize_state(solver, state):
-    """a lazy initial state (above) becomes what ``ADMM.initialize`` returns: v_i = K_i x0, u_i = 0, written into the same tensors"""
-    if not getattr(solver, "_fresh_lazy", False):
-        return
-    solver._fresh_lazy = False
-    if not fresh_state(solver, state):
+    """a lazy initial state (above) becomes what ``ADMM.initialize`` returns: v_i = K_i x0, u_i = 0, written into the same tensors
+    (any other state is left alone, and the marker with it)"""
+    if not (getattr(solver, "_fresh_lazy", False) and fresh_state(solver, state)):
         return
     x0, v, u = state
     kx = solver.K.forward(x0, return_list=True) or []
@@ -178,7 +196,7 @@ def materialize_state(solver, state):
         dst.copy_(src)
     for t in u:
         t.zero_()
-    solver._fresh = (x0, v, u, [t._version for t in [x0] + v + u])
+    set_fresh(solver, x0, v, u)
 
 
 def fresh_state(solver, state):
@@ -253,6 +271,35 @@ def _denoise_split(fn, d, sig):
     return den.model(d, sig)
 
 
+def _term_array(psi, codes, v, u, lam_tab=None):
+    """the C term array of the Psi terms over split variables v and duals u; lam: row 0 of the lambda tables, where they exist yet"""
+    return ops.make_terms([dict(linop=lc, prox=pc, alpha=float(fn.alpha), lam=None if lam_tab is None else lam_tab[i][0], v=v[i], u=u[i])
+                           for i, (fn, (lc, pc)) in enumerate(zip(psi, codes))])
+
+
+class _HostLoop:
+    """What the per-iteration host loops of the fused engines share.  Iterating yields the iteration number under the progress bar, with
+    this iteration's rows of the lambda tables set in ``terms`` (no tables: the C side walks them itself).  ``done`` ends an iteration:
+    the iterate becomes the variable's value and a callback sees the state -- a function, since every engine has its own (negated duals
+    for v-x-u, (x, v) for half-quadratic splitting, (x, z, xbar) for Pock-Chambolle) and only a callback makes it worth computing."""
+
+    def __init__(self, solver, T, rhos, lams, pbar, callback, terms=None, lam_tab=()):
+        self.solver, self.T, self.rhos, self.lams, self.pbar, self.callback = solver, T, rhos, lams, pbar, callback
+        self.terms, self.lam_tab = terms, lam_tab
+
+    def __iter__(self):
+        for it in tqdm(range(self.T), disable=not self.pbar):
+            for i, lt in enumerate(self.lam_tab):
+                self.terms[i].lam = lt[it].data_ptr()
+            yield it
+
+    def done(self, it, x, state):
+        self.solver.Kall.variables[0].value = x
+        if self.callback is not None:
+            self.solver._notify_all_op_current_step(it)
+            self.callback(iter=it, state=state(), rho=self.rhos[..., it], lam={k: val[..., it] for k, val in self.lams.items()})
+
+
 def plan_split_cg(solver, state, rhos, lams):
     """ADMM / LinearizedADMM whose x-update is a CG solve (the stacked operator is not diagonalisable: config 4's subsampled
     Fourier data term) and whose Psi terms all act on x itself.  Returns a FusedSplitCG or None."""
@@ -311,12 +358,9 @@ class FusedSplitCG:
         u = [t.contiguous() for t in u]
         x = x0
         rhs = torch.empty_like(x0)
-        specs = [dict(linop=lc, prox=pc, alpha=float(fn.alpha), lam=lam_tab[i][0], v=v[i], u=u[i])
-                 for i, (fn, (lc, pc)) in enumerate(zip(psi, self.codes))]
-        terms = ops.make_terms(specs)
-        n = len(specs)
+        terms, n = _term_array(psi, self.codes, v, u, lam_tab), len(psi)
         ext = [i for i, (_, pc) in enumerate(self.codes) if pc == be.PROX_EXTERNAL]
-        var = s.Kall.variables[0]
+        loop = _HostLoop(s, T, rhos, lams, pbar, callback, terms, lam_tab)
         ktb = ls.quad_rhs()
         if ktb is not None and ktb.shape != x0.shape:
             ktb = ktb.expand_as(x0).contiguous()
@@ -339,9 +383,7 @@ class FusedSplitCG:
             hist, run_hist = list(getattr(s, "_cg_exit_hist", ())), []
             s._cg_exit_hist = run_hist
             xs = (x, torch.empty_like(x0)) if step.folds else (x, x)  # (folded tail: iteration t + 1's iterate is zeroed while x_t is still the result)
-            for it in tqdm(range(T), disable=not pbar):
-                for i in range(n):
-                    terms[i].lam = lam_tab[i][it].data_ptr()
+            for it in loop:
                 x = xs[it & 1]
                 hint = hist[it] if it < len(hist) else -1            # (where the same solve of this solver's previous run ended)
                 if step.folds and it + 1 < T and callback is None:     # (a callback may solve something else in between: the prepared CG state lives in a shared workspace)
@@ -352,17 +394,12 @@ class FusedSplitCG:
                 run_hist.append(n_cg)
                 v[e], v_new = v_new, v[e]                            # the denoised image becomes v; its old buffer is the next target
                 terms[e].v = v[e].data_ptr()
-                var.value = x
-                if callback is not None:
-                    s._notify_all_op_current_step(it)
-                    callback(iter=it, state=(x, v, u), rho=rhos[..., it], lam={k: val[..., it] for k, val in lams.items()})
-                    if net_key() != step_key:                        # the callback touched the denoiser (weights / arithmetic mode): resolve the
-                        step, step_key = ops.CgPnpIter(xs[0], rhs, ktb, terms, n, e, sysm[0], sysm[1], cfg.rtol, cfg.max_iters, net), net_key()   # packed weights again
+                loop.done(it, x, lambda: (x, v, u))
+                if callback is not None and net_key() != step_key:   # the callback touched the denoiser (weights / arithmetic mode): resolve the
+                    step, step_key = ops.CgPnpIter(xs[0], rhs, ktb, terms, n, e, sysm[0], sysm[1], cfg.rtol, cfg.max_iters, net), net_key()   # packed weights again
             s.Kall.update_vars([x])
             return x, v, u
-        for it in tqdm(range(T), disable=not pbar):
-            for i in range(n):
-                terms[i].lam = lam_tab[i][it].data_ptr()
+        for it in loop:
             ops.admm_rhs(rhs, ktb, rho_tab[it], terms, n)
             x = ls.solve_cg_rhs(rhs, rho_tab[it])
             ops.admm_zupdate(x, terms, n)
@@ -372,10 +409,7 @@ class FusedSplitCG:
                 ops.lincomb([(1.0, d), (-1.0, out)], out=u[i])       # u_i = d - v_i
                 v[i] = out
                 terms[i].v = out.data_ptr()
-            var.value = x
-            if callback is not None:
-                s._notify_all_op_current_step(it)
-                callback(iter=it, state=(x, v, u), rho=rhos[..., it], lam={k: val[..., it] for k, val in lams.items()})
+            loop.done(it, x, lambda: (x, v, u))
         s.Kall.update_vars([x])
         return x, v, u
 
@@ -462,6 +496,12 @@ def chain_bounds(B, chains, c):
     return (c * B) // chains, ((c + 1) * B) // chains
 
 
+def usable_chains(x):
+    """sub_batch_chains of x's shape; 1 where the device has no second hardware queue for a second chain to run on"""
+    chains = sub_batch_chains(*x.shape) if (x.is_cuda or be.host_mode()) else 1
+    return chains if chains > 1 and chain_stream_handles(x.device, chains) is not None else 1
+
+
 def sub_batch_chains(B, C, H, W):
     """how many independent sub-batch chains the two-kernel iteration of a [B,C,H,W] problem is run as (FusedADMM._run_chains): 2 when
     each half still fills the GPU by itself (measured on 2 ... 16 images of 1 ... 3 x 512^2 ... 1024^2, tools/concurrent_probe.py,
@@ -476,8 +516,27 @@ def sub_batch_chains(B, C, H, W):
     return 1
 
 
+# The engines of FusedADMM.run: ``route`` names one per solve, ``_run`` dispatches on the name, ``solver.last_engine`` keeps it.
+ENGINES = {
+    "autograd":       "_run_autograd: autodiff.run -- dpx_admm_unrolled_forward[_bf16] / _backward, or every stage an autograd node",
+    "two_kernel":     "_run_two_kernel: dpx_admm_seed_rows[_fresh], dpx_admm_run (one stream)",
+    "chains":         "_seed_chains + _run_chains: dpx_admm_seed_rows[_fresh] per chain, dpx_admm_run_chains, dpx_stream_fork / _join",
+    "vxu_two_kernel": "_run_vxu_two_kernel: dpx_admm_zupdate, dpx_admm_seed_rows, dpx_admm_run[_chains], dpx_admm_rhs, dpx_fourier_solve",
+    "vxu_staged":     "_run_vxu_staged: dpx_admm_zupdate_rhs | dpx_admm_zupdate + dpx_admm_rhs, dpx_fourier_solve, dpx_lincomb",
+    "pnp_one_call":   "_run_pnp_one_call: dpx_admm_pnp_iter",
+    "staged":         "_run_staged: dpx_admm_rhs, dpx_fourier_solve, dpx_admm_zupdate[_rhs] (merge_z_rhs), the external terms' denoisers",
+    "stencil_ladmm":  "run_stencil (its caller's choice, not route's): dpx_split_rhs, dpx_fourier_solve, dpx_admm_zupdate",
+    "stencil_pc":     "run_stencil (likewise): dpx_pc_dual, dpx_split_rhs, dpx_fourier_solve, dpx_lincomb",
+}
+
+
+def _psf_is_trained(cv):
+    """True for the conv node of an Omega term whose PSF is trained through the solver: a circular conv_doe over a PSF that requires grad"""
+    return isinstance(cv, conv_doe) and cv.circular and isinstance(cv.psf, torch.Tensor) and cv.psf.requires_grad
+
+
 class FusedADMM:
-    merge_z_rhs = True      # staged iteration (planes off the two-kernel iteration): z / dual stage + next right-hand side as one pass
+    merge_z_rhs = True     # staged iteration (planes off the two-kernel iteration): z / dual stage + next right-hand side as one pass
 
     def __init__(self, solver, codes):
         self.solver, self.codes = solver, codes
@@ -503,8 +562,7 @@ class FusedADMM:
         """(the Omega terms' offsets as autograd tensors, the trained PSFs, whether autograd asks this solve for any gradient)"""
         s = self.solver
         raw_offs = [self._offset_autograd(fn, x0) for fn in s.omega_fns]
-        trained_psfs = [cv.psf for cv in map(_omega_conv, s.omega_fns)
-                        if isinstance(cv, conv_doe) and cv.circular and isinstance(cv.psf, torch.Tensor) and cv.psf.requires_grad]
+        trained_psfs = [cv.psf for cv in map(_omega_conv, s.omega_fns) if _psf_is_trained(cv)]
         return raw_offs, trained_psfs, autodiff.needs_grad(x0, rhos, lams, raw_offs, list(v) + list(u) + trained_psfs)
 
     def differentiates_tv_prior(self, state, rhos, lams):
@@ -513,8 +571,23 @@ class FusedADMM:
         and dpx_tv_backward) -- never the no-gradient stages"""
         if not differentiable_tv_priors(self.solver.psi_fns):
             return False
-        x0, v, u = state
-        return self._grad_request(x0, v, u, rhos, lams)[2]
+        return self._grad_request(*state, rhos, lams)[2]
+
+    def route(self, x0, T, dual, vxu, want_grad, watched):
+        """the engine (ENGINES) of a solve of T > 0 iterations from x0.  want_grad: autograd asks this solve for a gradient; watched: a
+        callback or a progress bar looks at every iteration.  The one place that decides: ``_run`` only compares names afterwards."""
+        if want_grad:
+            return "autograd"
+        C, H, W = x0.shape[1:]
+        if two_kernel_takes(self.codes, H, W):
+            if vxu:                                              # (its loop runs one v-update ahead of the iteration boundaries and ends on staged kernels)
+                return "vxu_two_kernel" if T >= 3 and not watched else "vxu_staged"
+            return "chains" if not watched and usable_chains(x0) > 1 else "two_kernel"
+        ext = [fn for fn, (_, pc) in zip(self.solver.psi_fns, self.codes) if pc == be.PROX_EXTERNAL]
+        if vxu or not dual or len(ext) != 1 or torch.is_grad_enabled():
+            return "vxu_staged" if vxu else "staged"
+        den = getattr(ext[0], "denoiser", None)                  # one FFDNet prior, everything else closed-form: one C call per iteration
+        return "pnp_one_call" if isinstance(den, (FFDNetColorDenoiser, FFDNetDenoiser)) and den.model.in_nc in (C, 1) else "staged"
 
     def _run(self, state, rhos, lams, max_iter, pbar=False, callback=None, dual=True, vxu=False):
         """``dual=False``: half-quadratic splitting (hqs.py:4-20) = the same three stages with the dual variables pinned to
@@ -522,23 +595,15 @@ class FusedADMM:
         ``vxu=True``: ADMM in the order v, x, u (admm.py:103-120) on the same stages: with u' = -u the split update is
         prox(K z + u') (z stage, its dual output discarded), the x-update sees v - u', and u' <- u' - v + z is one AXPY."""
         _tr("enter")
-        s = self.solver
-        ls = s.least_square
-        psi = list(s.psi_fns)
-        if dual:
-            x0, v, u = state
-        else:
-            x0, v = state
-            zero = torch.zeros_like(x0)
-            u = [zero for _ in v]
-        B, C, H, W = x0.shape
-        dev = x0.device
-        T = max_iter
+        s, psi = self.solver, list(self.solver.psi_fns)
+        x0, v = state[0], state[1]
+        u = state[2] if dual else [torch.zeros_like(x0)] * len(v)
+        (B, C, H, W), dev, T = x0.shape, x0.device, max_iter
         s.Kall.update_vars([x0])
+        s.last_engine = None                                 # (tests / tools: the engine of the last solve; None: there was nothing to run)
         if T <= 0:                                           # nothing to do: the state is returned as it came
             materialize_state(s, state)
             return state
-
         raw_offs, trained_psfs, want_grad = self._grad_request(x0, v, u, rhos, lams)
         want_grad = dual and not vxu and want_grad
         # a TVDenoiser(differentiable=True) prior whose gradient is asked for never meets the no-gradient stages below (they would run its
@@ -547,159 +612,139 @@ class FusedADMM:
         # (the differentiable path builds its own schedule tables as autograd nodes, autodiff.run: none are made here for it)
         rho_tab = None if want_grad else schedule_table(rhos, T, B, dev)
         _tr("rho table")
+        _tr("grad checks")
+        engine = s.last_engine = self.route(x0, T, dual, vxu, want_grad, callback is not None or pbar)
+        chains = usable_chains(x0) if engine == "chains" else 1
+        fresh = dual and not vxu and fresh_state(s, state)
+        lazy = fresh and getattr(s, "_fresh_lazy", False)      # (a lazy state: two_kernel_takes said yes to it, so every no-gradient solve seeds from x0)
+        # the differentiable path may keep a lazy state when nothing is differentiated THROUGH the state and the whole loop is one C call on
+        # the two-kernel iteration (autodiff._UnrolledClosed): the C side then forms the first right-hand side from x0 (dpx_admm_rhs_fresh)
+        grad_fresh = lazy and want_grad and not x0.requires_grad and not trained_psfs and not os.environ.get("DPX_UNROLL_CHAIN")
+        if lazy and want_grad and not grad_fresh:              # (a path that reads the split variables)
+            materialize_state(s, state)
+        clear_fresh(s)                                         # (the state is about to be advanced in place)
         # The two-kernel iteration starts from the row-transformed right-hand side rho_0 sum K_i^T (v_i - u_i): that pass needs
         # nothing but the state, so it is launched FIRST and the rest of the host-side preparation (schedule tables, data spectrum,
         # denominators, workspaces: ~0.1 ms) runs while the GPU is already busy instead of in front of it.
-        _tr("grad checks")
         seeded = None
-        chains = 1
-        if callback is None and not pbar and not vxu and torch.is_tensor(x0) and (x0.is_cuda or be.host_mode()):
-            chains = sub_batch_chains(B, C, H, W)
-            if chains > 1 and chain_stream_handles(dev, chains) is None:      # (no second hardware queue to run on)
-                chains = 1
-        fresh = dual and not vxu and fresh_state(s, state)
-        lazy = fresh and getattr(s, "_fresh_lazy", False)
-        # the differentiable path may keep a lazy state when nothing is differentiated THROUGH the state and the whole loop is one C call on
-        # the two-kernel iteration (autodiff._UnrolledClosed): the C side then forms the first right-hand side from x0 (dpx_admm_rhs_fresh)
-        grad_fresh = (lazy and want_grad and T > 0 and len(psi) > 0 and not x0.requires_grad and not trained_psfs
-                      and all(pc != be.PROX_EXTERNAL for _, pc in self.codes) and not os.environ.get("DPX_UNROLL_CHAIN"))
-        if lazy and not grad_fresh and (want_grad or T <= 0 or len(psi) == 0):     # (a path that reads the split variables)
-            materialize_state(s, state)
-            lazy = False
-        s._fresh = None                                        # (the state is about to be advanced in place)
-        s._fresh_lazy = False
-        if not want_grad and not vxu and len(psi) > 0 and all(pc != be.PROX_EXTERNAL for _, pc in self.codes):
-            v = [t.contiguous() for t in v]
-            u = [t.contiguous() for t in u]
-            early = ops.make_terms([dict(linop=lc, prox=pc, alpha=float(fn.alpha), lam=None, v=v[i], u=u[i])
-                                    for i, (fn, (lc, pc)) in enumerate(zip(psi, self.codes))])
-            if ops.iter_supported(H, W, early, len(psi)):
-                if chains > 1:                                     # (every chain seeds its own spectrum buffer on its own stream, now)
-                    seeded = self._seed_chains(x0, v, u, rho_tab, fresh, chains, dev)
-                else:
-                    seeded = ops.admm_seed_rows(ops.spectrum_buffer(B * C, H, W, dev), rho_tab[0], early, len(psi), x0.shape, dev,
-                                                fresh_x=x0 if fresh else None)
+        if engine in ("two_kernel", "chains"):
+            v, u = [t.contiguous() for t in v], [t.contiguous() for t in u]
+            if engine == "chains":                             # (every chain seeds its own spectrum buffer on its own stream, now)
+                seeded = self._seed_chains(x0, v, u, rho_tab, fresh, chains, dev)
+            else:
+                seeded = ops.admm_seed_rows(ops.spectrum_buffer(B * C, H, W, dev), rho_tab[0], _term_array(psi, self.codes, v, u), len(psi),
+                                            x0.shape, dev, fresh_x=x0 if fresh else None)
         _tr("seeds issued")
-        if not isinstance(seeded, dict):
-            chains = 1
-        if lazy and seeded is None and not grad_fresh:         # (cannot happen for a state lazy_initial_state handed out; kept as a guard)
-            s._fresh, s._fresh_lazy = (x0, list(v), list(u), [t._version for t in [x0] + list(v) + list(u)]), True
-            materialize_state(s, state)
-            s._fresh, fresh = None, False
-        lam_tab = []
-        for fn in (() if want_grad else psi):
-            lt = schedule_table(lams[fn], T, B, dev)
-            lam_tab.append(_lam_table(fn, lt))                    # priors: the table holds sigma
+        lam_tab = [] if want_grad else [_lam_table(fn, schedule_table(lams[fn], T, B, dev)) for fn in psi]      # (priors: the table holds sigma)
         # data spectrum F(sum_Omega K^T b): fp64 transform, kept in the Fourier domain, recomputed only when an
         # offset (the observation b) changes
         _tr("lam tables")
         FK = self._data_spectrum(x0, chains)
         _tr("data spectrum")
-        (t0, c0), (t1, c1) = ls.diag_tables(x0.shape, dev, True)
+        (t0, c0), (t1, c1) = s.least_square.diag_tables(x0.shape, dev, True)
+        diag = (t0, c0, t1, c1)
         _tr("diag tables")
+        if engine == "autograd":
+            return self._run_autograd((x0, v, u), rhos, lams, T, raw_offs, FK, diag, grad_fresh)
+        p = SimpleNamespace(x0=x0, T=T, dual=dual, FK=FK, diag=diag, rho_tab=rho_tab, lam_tab=lam_tab, v=[t.contiguous() for t in v],
+                            u=[t.contiguous() for t in u], x=torch.empty_like(x0),
+                            rhs=None if seeded is not None else torch.empty_like(x0))     # (the two-kernel iteration never forms the right-hand side as an image)
+        p.solve = lambda rhs, rho, out: ops.fourier_solve(rhs, t0, t1, c0, c1, rho, ls_eps(s.least_square), out=out, spec_add=FK)
+        self._build_terms(p, vxu)
+        # (the two-kernel iteration walks the lambda tables on the C side: its host loop sets no rows)
+        p.loop = _HostLoop(s, T, rhos, lams, pbar, callback, p.terms, () if engine == "two_kernel" else lam_tab)
+        if engine == "vxu_two_kernel":
+            return self._run_vxu_two_kernel(x0.shape, dev, T, p.terms, p.n, p.v, p.u, p.x, FK, diag, rho_tab, lam_tab)
+        if engine in ("vxu_staged", "pnp_one_call", "staged"):
+            return getattr(self, "_run_" + engine)(p)
+        assert engine in ("two_kernel", "chains"), engine
+        if not dual:                                             # half-quadratic splitting: the same two kernels with the duals counted as zero
+            for i in range(p.n):
+                p.terms[i].reserved = be.TERM_NO_DUAL
+        _tr("terms built")
+        if engine == "chains":
+            return self._run_chains(x0, dev, T, p.n, p.v, p.u, p.x, FK, diag, rho_tab, lam_tab, dual, fresh, chains, seeded)
+        return self._run_two_kernel(p, seeded, fresh)
 
-        # ---- differentiable (unrolled-training) mode: hand-written backward stages, autodiff.py -------------------
-        if want_grad:
-            otfs, doe = [], []
-            for fn in s.omega_fns:
-                cv = _omega_conv(fn)
-                otfs.append(cv._tables(x0.shape, dev) if cv is not None else None)
-                if isinstance(cv, conv_doe) and cv.circular and isinstance(cv.psf, torch.Tensor) and cv.psf.requires_grad and torch.is_grad_enabled():
-                    # end-to-end optics: the PSF is trained through the solver -- its OTF enters the x-updates as an autograd tensor
-                    from ..linop.fourier import _doe_padded
-                    P = _doe_padded(cv.psf.float().to(dev), x0.shape).expand(1, C, H, W).contiguous()
-                    off = fn.offset
-                    Yhat = None if off is None else ops.cfft2(off.detach().to(dev).expand_as(x0).contiguous(), inverse=False, centred=False, ortho=False)
-                    doe.append((autodiff._FullOtf.apply(P), Yhat))
-            plan = autodiff.DiffPlan(self.codes, psi, (t0, c0, t1, c1), FK, otfs, ls_eps(ls), hist_bf16=getattr(s, "unroll_dtype", "f32") == "bf16",
-                                     doe=doe)
-            diff_offs = [o if o is not None else ops.zero_scalar(dev) for o in raw_offs]
-            if grad_fresh and not doe:
-                plan.fresh_x0 = x0
-            elif grad_fresh:                                       # (a trained PSF: the stage-by-stage path reads the state)
-                s._fresh, s._fresh_lazy = (x0, list(v), list(u), [t._version for t in [x0] + list(v) + list(u)]), True
-                materialize_state(s, state)
-                s._fresh = None
-            x, v, u = autodiff.run(plan, (x0, v, u), rhos, {fn: lams[fn] for fn in psi}, T, diff_offs)
-            s.Kall.update_vars([x.detach()])
-            return x, v, u
-
-        v = [t.contiguous() for t in v]
-        u = [t.contiguous() for t in u]
-        x = torch.empty_like(x0)
-        rhs = None if seeded is not None else torch.empty_like(x0)        # (the two-kernel iteration never forms the right-hand side as an image)
-        specs = [dict(linop=lc, prox=pc, alpha=float(fn.alpha), lam=lam_tab[i][0], v=v[i], u=u[i])
-                 for i, (fn, (lc, pc)) in enumerate(zip(psi, self.codes))]
-        terms = ops.make_terms(specs)
-        n = len(specs)
-        ext = [i for i, (_, pc) in enumerate(self.codes) if pc == be.PROX_EXTERNAL]
-        var = s.Kall.variables[0]
-
-        if not dual or vxu:
-            scratch = torch.empty_like(x0)
-            for i in range(n):
-                terms[i].u_out = scratch.data_ptr()
+    def _build_terms(self, p, vxu):
+        """the no-gradient engines' term array p.terms over the prepared state (p.ext: the terms whose prox is not closed-form), and what
+        both v-x-u engines start from: the iterate copied, the duals negated"""
+        p.terms, p.n = _term_array(self.solver.psi_fns, self.codes, p.v, p.u, p.lam_tab), len(self.codes)
+        p.ext = [i for i, (_, pc) in enumerate(self.codes) if pc == be.PROX_EXTERNAL]
+        if not p.dual or vxu:
+            p.scratch = torch.empty_like(p.x0)
+            for i in range(p.n):
+                p.terms[i].u_out = p.scratch.data_ptr()
         if vxu:
-            x.copy_(x0)
-            for i in range(n):                                   # u' = -u, kept in fresh buffers
-                u[i] = ops.lincomb([(-1.0, u[i])])
-                terms[i].u = u[i].data_ptr()
-            if callback is None and not pbar and T >= 3 and not ext and n > 0 and ops.iter_supported(H, W, terms, n):
-                return self._run_vxu_two_kernel(x0.shape, dev, T, terms, n, v, u, x, FK, (t0, c0, t1, c1), rho_tab, lam_tab)
-            for it in tqdm(range(T), disable=not pbar):
-                for i in range(n):
-                    terms[i].lam = lam_tab[i][it].data_ptr()
-                if n > 0 and not ext and self.merge_z_rhs:           # v-update and right-hand side of the same iteration: one pass (the duals
-                    ops.admm_zupdate_rhs(x, terms, n, rhs, rho_tab[it], dual=False)      # it would write go to scratch: rhs from the incoming ones)
-                else:
-                    ops.admm_zupdate(x, terms, n)
-                    ops.admm_rhs(rhs, None, rho_tab[it], terms, n)
-                ops.fourier_solve(rhs, t0, t1, c0, c1, rho_tab[it], ls_eps(ls), out=x, spec_add=FK)
-                for i in range(n):
-                    ops.lincomb([(1.0, u[i]), (-1.0, v[i]), (1.0, x)], out=u[i])
-                var.value = x
-                if callback is not None:
-                    s._notify_all_op_current_step(it)
-                    callback(iter=it, state=(x, v, [ops.lincomb([(-1.0, t)]) for t in u]), rho=rhos[..., it],
-                             lam={k: val[..., it] for k, val in lams.items()})
-            s.Kall.update_vars([x])
-            return x, v, [ops.lincomb([(-1.0, t)]) for t in u]
-        if not ext and n > 0 and ops.iter_supported(H, W, terms, n):
-            if not dual:                                         # half-quadratic splitting: the same two kernels with the duals counted as zero
-                for i in range(n):
-                    terms[i].reserved = be.TERM_NO_DUAL
-            _tr("terms built")
-            if chains > 1:
-                return self._run_chains(x0, dev, T, n, v, u, x, FK, (t0, c0, t1, c1), rho_tab, lam_tab, dual, fresh, chains, seeded)
-            return self._run_two_kernel(x0.shape, dev, T, terms, n, v, u, x, rhs, FK, (t0, c0, t1, c1), rho_tab, lam_tab,
-                                        rhos, lams, pbar, callback, dual, seeded, fresh and seeded is not None)
+            p.x.copy_(p.x0)
+            for i in range(p.n):                                 # u' = -u, kept in fresh buffers
+                p.u[i] = ops.lincomb([(-1.0, p.u[i])])
+                p.terms[i].u = p.u[i].data_ptr()
 
-        # one FFDNet prior, everything else closed-form: the whole iteration is ONE C call (dpx_admm_pnp_iter)
-        one_call = (dual and len(ext) == 1 and isinstance(getattr(psi[ext[0]], "denoiser", None), (FFDNetColorDenoiser, FFDNetDenoiser))
-                    and not torch.is_grad_enabled() and psi[ext[0]].denoiser.model.in_nc in (C, 1))
-        if one_call:
-            e = ext[0]
-            net = psi[e].denoiser.model
-            gray = net.in_nc != C
-            sig_tab = lam_tab[e].repeat_interleave(C, dim=1).contiguous() if (gray and C > 1) else lam_tab[e]
-            dd = ops.denominator(t0, c0, t1, c1, C, H, W, dev)
-            v_new = torch.empty_like(x0)
-            for it in tqdm(range(T), disable=not pbar):
-                for i in range(n):
-                    terms[i].lam = lam_tab[i][it].data_ptr()
-                ops.admm_pnp_iter(x, rhs, terms, n, e, v_new, rho_tab[it], sig_tab[it], FK, dd, ls_eps(ls), net)
-                v[e], v_new = v_new, v[e]                            # the denoised image becomes v; its old buffer is the next target
-                terms[e].v = v[e].data_ptr()
-                var.value = x
-                if callback is not None:
-                    s._notify_all_op_current_step(it)
-                    callback(iter=it, state=(x, v, u), rho=rhos[..., it], lam={k: val[..., it] for k, val in lams.items()})
-            s.Kall.update_vars([x])
-            return x, v, u
+    def _run_autograd(self, state, rhos, lams, T, raw_offs, FK, diag, fresh_x0):
+        """differentiable (unrolled-training) mode: hand-written backward stages, autodiff.py.  fresh_x0: the state is lazy and stays so
+        (``_run`` keeps one only where no PSF is trained: ``doe`` is empty then, and the loop is the one C call that never reads it)"""
+        s, psi, x0 = self.solver, list(self.solver.psi_fns), state[0]
+        (B, C, H, W), dev = x0.shape, x0.device
+        otfs, doe = [], []
+        for fn in s.omega_fns:
+            cv = _omega_conv(fn)
+            otfs.append(cv._tables(x0.shape, dev) if cv is not None else None)
+            if _psf_is_trained(cv) and torch.is_grad_enabled():
+                # end-to-end optics: the PSF is trained through the solver -- its OTF enters the x-updates as an autograd tensor
+                from ..linop.fourier import _doe_padded
+                P = _doe_padded(cv.psf.float().to(dev), x0.shape).expand(1, C, H, W).contiguous()
+                off = fn.offset
+                Yhat = None if off is None else ops.cfft2(off.detach().to(dev).expand_as(x0).contiguous(), inverse=False, centred=False, ortho=False)
+                doe.append((autodiff._FullOtf.apply(P), Yhat))
+        plan = autodiff.DiffPlan(self.codes, psi, diag, FK, otfs, ls_eps(s.least_square), hist_bf16=getattr(s, "unroll_dtype", "f32") == "bf16",
+                                 doe=doe)
+        diff_offs = [o if o is not None else ops.zero_scalar(dev) for o in raw_offs]
+        if fresh_x0:
+            plan.fresh_x0 = x0
+        x, v, u = autodiff.run(plan, state, rhos, {fn: lams[fn] for fn in psi}, T, diff_offs)
+        s.Kall.update_vars([x.detach()])
+        return x, v, u
 
-        # closed-form proxes only: the z / dual stage of iteration t and the right-hand side of iteration t + 1 are ONE pass
-        # (dpx_admm_zupdate_rhs: 8 instead of 12 plane passes; it reads duals at neighbouring pixels, so the duals alternate between two
-        # sets of buffers -- half-quadratic splitting's are write-only scratch already)
+    def _run_vxu_staged(self, p):
+        """ADMM in the order v, x, u on the staged kernels; p.u: the negated duals u'"""
+        x, v, u, rhs, terms, n, rho_tab = p.x, p.v, p.u, p.rhs, p.terms, p.n, p.rho_tab
+        for it in p.loop:
+            if n > 0 and not p.ext and self.merge_z_rhs:         # v-update and right-hand side of the same iteration: one pass (the duals
+                ops.admm_zupdate_rhs(x, terms, n, rhs, rho_tab[it], dual=False)      # it would write go to scratch: rhs from the incoming ones)
+            else:
+                ops.admm_zupdate(x, terms, n)
+                ops.admm_rhs(rhs, None, rho_tab[it], terms, n)
+            p.solve(rhs, rho_tab[it], x)
+            for i in range(n):
+                ops.lincomb([(1.0, u[i]), (-1.0, v[i]), (1.0, x)], out=u[i])
+            p.loop.done(it, x, lambda: (x, v, [ops.lincomb([(-1.0, t)]) for t in u]))
+        self.solver.Kall.update_vars([x])
+        return x, v, [ops.lincomb([(-1.0, t)]) for t in u]
+
+    def _run_pnp_one_call(self, p):
+        """one FFDNet prior, everything else closed-form: the whole iteration is ONE C call (dpx_admm_pnp_iter)"""
+        s, e = self.solver, p.ext[0]
+        x, v, u, terms, lam_tab = p.x, p.v, p.u, p.terms, p.lam_tab
+        B, C, H, W = p.x0.shape
+        net = list(s.psi_fns)[e].denoiser.model
+        sig_tab = lam_tab[e].repeat_interleave(C, dim=1).contiguous() if (net.in_nc != C and C > 1) else lam_tab[e]      # (a gray net: per plane)
+        dd = ops.denominator(*p.diag, C, H, W, p.x0.device)
+        v_new = torch.empty_like(p.x0)
+        for it in p.loop:
+            ops.admm_pnp_iter(x, p.rhs, terms, p.n, e, v_new, p.rho_tab[it], sig_tab[it], p.FK, dd, ls_eps(s.least_square), net)
+            v[e], v_new = v_new, v[e]                            # the denoised image becomes v; its old buffer is the next target
+            terms[e].v = v[e].data_ptr()
+            p.loop.done(it, x, lambda: (x, v, u))
+        s.Kall.update_vars([x])
+        return x, v, u
+
+    def _run_staged(self, p):
+        """rhs / Fourier solve / z stages, one call each.  Closed-form proxes only: the z / dual stage of iteration t and the right-hand
+        side of iteration t + 1 are ONE pass (dpx_admm_zupdate_rhs: 8 instead of 12 plane passes; it reads duals at neighbouring pixels,
+        so the duals alternate between two sets of buffers -- half-quadratic splitting's are write-only scratch already)"""
+        psi = list(self.solver.psi_fns)
+        x, v, u, rhs, terms, n, ext, dual, T, rho_tab = p.x, p.v, p.u, p.rhs, p.terms, p.n, p.ext, p.dual, p.T, p.rho_tab
         merged = n > 0 and not ext and self.merge_z_rhs
         if merged and not dual:                                      # half-quadratic splitting: the duals are zero -- the merged pass need not fetch them
             for i in range(n):
@@ -709,14 +754,12 @@ class FusedADMM:
             u_alt = [torch.empty_like(t) for t in u]
             for i in range(n):
                 terms[i].u_out = u_alt[i].data_ptr()
-        for it in tqdm(range(T), disable=not pbar):
-            for i in range(n):
-                terms[i].lam = lam_tab[i][it].data_ptr()
+        for it in p.loop:
             if not merged or it == 0:
                 ops.admm_rhs(rhs, None, rho_tab[it], terms, n)
-            ops.fourier_solve(rhs, t0, t1, c0, c1, rho_tab[it], ls_eps(ls), out=x, spec_add=FK)
+            p.solve(rhs, rho_tab[it], x)
             if merged and it + 1 < T:
-                ops.admm_zupdate_rhs(x, terms, n, rhs, rho_tab[it + 1], dual=dual, emit_v=callback is not None)   # (v: only a callback looks at it before the last stage)
+                ops.admm_zupdate_rhs(x, terms, n, rhs, rho_tab[it + 1], dual=dual, emit_v=p.loop.callback is not None)   # (v: only a callback looks at it before the last stage)
             else:
                 ops.admm_zupdate(x, terms, n)
             if merged and dual:
@@ -725,15 +768,12 @@ class FusedADMM:
                     terms[i].u, terms[i].u_out = u[i].data_ptr(), u_alt[i].data_ptr()
             for i in ext:                                            # v_i holds d = x + u_i
                 d = v[i]
-                out = _denoise_split(psi[i], d, lam_tab[i][it])
+                out = _denoise_split(psi[i], d, p.lam_tab[i][it])
                 if dual:                                             # (half-quadratic splitting: the duals stay zero)
                     ops.lincomb([(1.0, d), (-1.0, out)], out=u[i])   # u_i = d - v_i
                 v[i] = out
                 terms[i].v = out.data_ptr()
-            var.value = x
-            if callback is not None:
-                s._notify_all_op_current_step(it)
-                callback(iter=it, state=(x, v, u) if dual else (x, v), rho=rhos[..., it], lam={k: val[..., it] for k, val in lams.items()})
+            p.loop.done(it, x, lambda: (x, v, u) if dual else (x, v))
         if merged and dual:
             # the duals alternated between the caller's tensors and u_alt: after an odd number of iterations the current ones sit in
             # u_alt -- they go back into the tensors that came in, so that a caller holding on to its state's duals sees this call's
@@ -742,9 +782,8 @@ class FusedADMM:
                 if u[i] is not u_given[i]:
                     u_given[i].copy_(u[i])
                     u[i] = u_given[i]
-        s.Kall.update_vars([x])
+        self.solver.Kall.update_vars([x])
         return (x, v, u) if dual else (x, v)
-
 
     def _run_vxu_two_kernel(self, shape, dev, T, terms, n, v, up, x, FK, diag, rho_tab, lam_tab):
         """ADMM in the order v, x, u (admm.py:103-120) on the two-kernel iteration (power-of-two planes, closed-form proxes, no callback).
@@ -754,11 +793,9 @@ class FusedADMM:
         rho_{j+1} sum K_i^T (v_i - u'_i): one plane in, one plane out per term like ADMM (DPX_TERM_VXU).  The first v-update and the
         last x-update / dual are the staged kernels (the loop is one v-update ahead of the reference's iteration boundaries).
         up: the negated duals u'.  Returns (z, [v_i], [u_i])."""
-        s = self.solver
-        ls = s.least_square
+        s, ls = self.solver, self.solver.least_square
         B, C, H, W = shape
         t0, c0, t1, c1 = diag
-        var = s.Kall.variables[0]
         scratch = torch.empty_like(x)
         # v-update of iteration 0 (dpx_admm_zupdate: v = prox(K x + u'); its dual output is not used)
         for i in range(n):
@@ -766,9 +803,7 @@ class FusedADMM:
             terms[i].u_out = scratch.data_ptr()
         ops.admm_zupdate(x, terms, n)
         # seed: row transform of rho_0 sum K^T (v - u'), then q = u' - v in place of u'
-        chains = sub_batch_chains(B, C, H, W) if (x.is_cuda or be.host_mode()) else 1
-        if chains > 1 and chain_stream_handles(dev, chains) is None:
-            chains = 1
+        chains = usable_chains(x)
         dd = ops.denominator(t0, c0, t1, c1, C, H, W, dev)
         if chains > 1:
             # sub-batch chains (_run_chains): every chain seeds from its images of (v, u') and walks its own spectrum buffers
@@ -794,8 +829,7 @@ class FusedADMM:
             finally:
                 L.call("dpx_admm_iter_share", 1)
         else:
-            SA = ops.spectrum_buffer(B * C, H, W, dev)
-            SB = ops.spectrum_buffer(B * C, H, W, dev)
+            SA, SB = ops.spectrum_buffer(B * C, H, W, dev), ops.spectrum_buffer(B * C, H, W, dev)
             ops.admm_seed_rows(SA, rho_tab[0], terms, n, shape, dev)
             q_cur = [ops.lincomb([(1.0, up[i]), (-1.0, v[i])]) for i in range(n)]
             q_nxt = [torch.empty_like(t) for t in q_cur]
@@ -817,7 +851,6 @@ class FusedADMM:
         ops.admm_rhs(rhs, None, rho_tab[T - 1], terms, n)
         ops.fourier_solve(rhs, t0, t1, c0, c1, rho_tab[T - 1], ls_eps(ls), out=x, spec_add=FK)
         u_out = [ops.lincomb([(-1.0, upf[i]), (1.0, v[i]), (-1.0, x)]) for i in range(n)]          # u = -(u' - v + z)
-        var.value = x
         s.Kall.update_vars([x])
         return x, v, u_out
 
@@ -828,12 +861,9 @@ class FusedADMM:
         z / dual stage is ``dpx_admm_zupdate`` (LADMM) or ``dpx_pc_dual`` (PC).  Closed-form proxes only; 3-4 passes per iteration
         instead of 10-15."""
         s = self.solver
-        ls = s.least_square
-        psi = list(s.psi_fns)
-        x0 = state[0]
-        B, C, H, W = x0.shape
-        dev = x0.device
-        T = max_iter
+        ls, psi = s.least_square, list(s.psi_fns)
+        x0, T = state[0], max_iter
+        (B, C, H, W), dev = x0.shape, x0.device
         s.Kall.update_vars([x0])
         if T <= 0:
             return state
@@ -841,46 +871,32 @@ class FusedADMM:
         lam_tab = [schedule_table(lams[fn], T, B, dev) for fn in psi]
         FK = self._data_spectrum(x0)
         (t0, c0), (t1, c1) = ls.diag_tables(x0.shape, dev, True)
-        n = len(psi)
-        var = s.Kall.variables[0]
-        rhs = torch.empty_like(x0)
+        n, rhs = len(psi), torch.empty_like(x0)
+        s.last_engine = "stencil_" + method
         if method == "ladmm":
-            _, v, u = state
             x = x0.clone()
-            v, u = [t.contiguous() for t in v], [t.contiguous() for t in u]
-            specs = [dict(linop=lc, prox=pc, alpha=float(fn.alpha), lam=lam_tab[i][0], v=v[i], u=u[i]) for i, (fn, (lc, pc)) in enumerate(zip(psi, self.codes))]
-            terms = ops.make_terms(specs)
-            for it in tqdm(range(T), disable=not pbar):
-                for i in range(n):
-                    terms[i].lam = lam_tab[i][it].data_ptr()
+            v, u = [t.contiguous() for t in state[1]], [t.contiguous() for t in state[2]]
+            terms = _term_array(psi, self.codes, v, u, lam_tab)
+            loop = _HostLoop(s, T, rhos, lams, pbar, callback, terms, lam_tab)
+            for it in loop:
                 ops.split_rhs(rhs, None, x, rho_tab[it], terms, n, 1)
                 ops.fourier_solve(rhs, t0, t1, c0, c1, rho_tab[it], ls_eps(ls), out=x, spec_add=FK)
                 ops.admm_zupdate(x, terms, n)
-                var.value = x
-                if callback is not None:
-                    s._notify_all_op_current_step(it)
-                    callback(iter=it, state=(x, v, u), rho=rhos[..., it], lam={k: val[..., it] for k, val in lams.items()})
+                loop.done(it, x, lambda: (x, v, u))
             s.Kall.update_vars([x])
             return x, v, u
         # Pock-Chambolle: state (x, [z_i], xbar)
-        _, z, xbar = state
-        x, xn = x0.clone(), torch.empty_like(x0)
-        xbar = xbar.clone()
-        z = [t.contiguous() for t in z]
-        specs = [dict(linop=lc, prox=pc, alpha=float(fn.alpha), lam=lam_tab[i][0], v=z[i], u=z[i]) for i, (fn, (lc, pc)) in enumerate(zip(psi, self.codes))]
-        terms = ops.make_terms(specs)
-        for it in tqdm(range(T), disable=not pbar):
-            for i in range(n):
-                terms[i].lam = lam_tab[i][it].data_ptr()
+        x, xn, xbar = x0.clone(), torch.empty_like(x0), state[2].clone()
+        z = [t.contiguous() for t in state[1]]
+        terms = _term_array(psi, self.codes, z, z, lam_tab)
+        loop = _HostLoop(s, T, rhos, lams, pbar, callback, terms, lam_tab)
+        for it in loop:
             ops.pc_dual(xbar, terms, n)                                  # z += r K xbar ; z -= r prox(z, r)
             ops.split_rhs(rhs, None, x, rho_tab[it], terms, n, 0)        # rho sum K^T (x - K^T z)
             ops.fourier_solve(rhs, t0, t1, c0, c1, rho_tab[it], ls_eps(ls), out=xn, spec_add=FK)
             ops.lincomb([(2.0, xn), (-1.0, x)], out=xbar)
             x, xn = xn, x
-            var.value = x
-            if callback is not None:
-                s._notify_all_op_current_step(it)
-                callback(iter=it, state=(x, z, xbar), rho=rhos[..., it], lam={k: val[..., it] for k, val in lams.items()})
+            loop.done(it, x, lambda: (x, z, xbar))
         s.Kall.update_vars([x])
         return x, z, xbar
 
@@ -1014,9 +1030,7 @@ class FusedADMM:
         _seed_chains prepared (the seed passes are already running)."""
         s = self.solver
         B, C, H, W = x0.shape
-        t0, c0, t1, c1 = diag
-        dd = ops.denominator(t0, c0, t1, c1, C, H, W, dev)
-        var = s.Kall.variables[0]
+        dd = ops.denominator(*diag, C, H, W, dev)
         eps = ls_eps(s.least_square)
         x_only = bool(getattr(s, "_x_only", False))
         if dual:
@@ -1052,47 +1066,36 @@ class FusedADMM:
             L.call("dpx_admm_iter_share", 1)
         if par:
             u_cur, u_nxt = u_nxt, u_cur
-        var.value = x
         s.Kall.update_vars([x])
         return (x, v, u_cur) if dual else (x, v)
 
-    def _run_two_kernel(self, shape, dev, T, terms, n, v, u, x, rhs, FK, diag, rho_tab, lam_tab, rhos, lams, pbar, callback, dual=True, seeded=None,
-                        fresh=False):
-        """power-of-two planes: cols -> rows, two kernels per iteration; x / v only leave the chip on request.
+    def _run_two_kernel(self, p, SA, fresh):
+        """power-of-two planes: cols -> rows, two kernels per iteration; x / v only leave the chip on request.  SA: the seeded spectrum.
         dual=False (half-quadratic splitting): u holds one shared all-zero buffer per term; the kernels' dual output goes to one
         shared scratch buffer and is ignored when it comes back as input (DPX_TERM_NO_DUAL)"""
         s = self.solver
-        B, C, H, W = shape
-        t0, c0, t1, c1 = diag
-        dd = ops.denominator(t0, c0, t1, c1, C, H, W, dev)
-        SA = seeded if seeded is not None else ops.spectrum_buffer(B * C, H, W, dev)     # (run() launches the seed pass first)
+        x, v, u, terms, n, dual, T, FK, rho_tab, lam_tab, loop = p.x, p.v, p.u, p.terms, p.n, p.dual, p.T, p.FK, p.rho_tab, p.lam_tab, p.loop
+        shape, dev, (B, C, H, W) = p.x0.shape, p.x0.device, p.x0.shape
+        dd = ops.denominator(*p.diag, C, H, W, dev)
         SB = ops.spectrum_buffer(B * C, H, W, dev)
         if dual:
             u_cur, u_nxt = list(u), [torch.empty_like(t) for t in u]
         else:
             u_cur, u_nxt = list(u), [torch.zeros_like(u[0])] * n
-        var = s.Kall.variables[0]
-        if T == 0:
-            return (var.value, v, u) if dual else (var.value, v)
-        # seed: row transform of the first right-hand-side increment rho_0 * sum K_i^T (v_i - u_i)
-        for i in range(n):
-            terms[i].lam = lam_tab[i][0].data_ptr()
-        if seeded is None:
-            ops.admm_seed_rows(SA, rho_tab[0], terms, n, shape, dev)
         for i in range(n):
             terms[i].u, terms[i].u_out, terms[i].v = u_cur[i].data_ptr(), u_nxt[i].data_ptr(), v[i].data_ptr()
         eps = ls_eps(s.least_square)
         if fresh:                                                # u_i = 0: the first iteration does not stream the duals (DPX_TERM_U_ZERO)
             for i in range(n):
                 terms[i].reserved |= be.TERM_U_ZERO
-        if callback is None and not pbar:
+        if loop.callback is None and not loop.pbar:
             # (solve() hands back x alone: the last pass then stores nothing else -- no v, no final dual update: emit mode 2)
             par = ops.admm_run(SA, SB, FK, dd, terms, n, rho_tab, lam_tab, eps, 0, T, T, x, 2 if getattr(s, "_x_only", False) else 1, shape, dev)
             if par:
                 u_cur, u_nxt = u_nxt, u_cur
         else:
-            for it in tqdm(range(T), disable=not pbar):
-                emit = callback is not None or it == T - 1
+            for it in loop:
+                emit = loop.callback is not None or it == T - 1
                 par = ops.admm_run(SA, SB, FK, dd, terms, n, rho_tab, lam_tab, eps, it, 1, T, x, emit, shape, dev)
                 for i in range(n):
                     terms[i].reserved &= ~be.TERM_U_ZERO
@@ -1101,10 +1104,7 @@ class FusedADMM:
                     for i in range(n):
                         terms[i].u, terms[i].u_out = u_cur[i].data_ptr(), u_nxt[i].data_ptr()
                 if emit:
-                    var.value = x
-                if callback is not None:
-                    s._notify_all_op_current_step(it)
-                    callback(iter=it, state=(x, v, u_cur) if dual else (x, v), rho=rhos[..., it], lam={k: val[..., it] for k, val in lams.items()})
+                    loop.done(it, x, lambda: (x, v, u_cur) if dual else (x, v))
         s.Kall.update_vars([x])
         return (x, v, u_cur) if dual else (x, v)
 

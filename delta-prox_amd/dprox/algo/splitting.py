@@ -66,7 +66,10 @@ class ADMM(Algorithm):
         v = [e if e is not x else e.clone() for e in v]
         u = [torch.zeros_like(e) for e in v]
         # the fused path recognises this state as long as nobody has written to it (fused.fresh_state): v_i = K_i x0, u_i = 0 exactly
-        self._fresh = (x, v, u, [t._version for t in [x] + v + u]) if derived and all(isinstance(t, torch.Tensor) for t in [x] + v) else None
+        if derived and all(isinstance(t, torch.Tensor) for t in [x] + v):
+            fused.set_fresh(self, x, v, u)
+        else:
+            fused.clear_fresh(self)
         return x, v, u
 
     def _plan_for(self, x):
@@ -109,7 +112,7 @@ class ADMM(Algorithm):
                 self.last_path = "fused"
                 return plan.run_stencil(state, rhos, lams, max_iter, "ladmm", pbar, callback)
         self.last_path = "generic"
-        self._fresh = None
+        fused.clear_fresh(self)
         return super().iters(state, rhos, lams, max_iter, pbar, callback)
 
     def _prox_dual(self, Kx, v, u, lam):
