@@ -255,6 +255,15 @@ SIGNATURES = {
     "dpx_lp_pcg_iters": (c_int, [c_void_p, c_long, c_long, c_long, c_double, c_double, c_long, c_int, c_void_p]),
     "dpx_lp_tail": (c_int, [c_void_p, c_long, c_long, c_long, c_double, c_double, c_void_p]),
     "dpx_lp_eval": (c_int, [c_void_p, c_long, c_long, c_long, c_double, c_double, c_void_p]),
+    "dpx_qrnn3d_packed_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "dpx_qrnn3d_pack": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    "dpx_qrnn3d_layer_ws_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int]),
+    "dpx_qrnn3d_layer": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+                                 c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "dpx_grunet_packed_bytes": (c_size_t, [c_int, c_int]),
+    "dpx_grunet_pack": (c_int, [c_void_p, POINTER(c_void_p), c_void_p, c_int, c_int, c_void_p]),
+    "dpx_grunet_ws_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "dpx_grunet_forward": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
 }
 
 

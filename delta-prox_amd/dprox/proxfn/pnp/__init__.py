@@ -1,2 +1,2 @@
-from .denoisers import Denoiser, Denoiser2D, DRUNetDenoiser, FFDNet, FFDNetColorDenoiser, FFDNetDenoiser, IRCNN, IRCNNDenoiser, TVDenoiser, UNet, UNetDenoiser, UNetRes
+from .denoisers import Denoiser, Denoiser2D, DRUNetDenoiser, FFDNet, FFDNetColorDenoiser, FFDNetDenoiser, GRUnet, GRUNetDenoiser, GRUNetTVDenoiser, IRCNN, IRCNNDenoiser, QRNN3DDenoiser, TVDenoiser, UNet, UNetDenoiser, UNetRes
 from .prior import deep_prior, get_denoiser

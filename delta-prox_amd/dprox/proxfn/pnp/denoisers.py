@@ -982,3 +982,163 @@ class IRCNNDenoiser(Denoiser2D):
             self.model = self.model.to(dev)
         self.former_idx = current_idx
         return self.model(x)
+
+
+# ---- GRUNet: the hyperspectral denoiser of the reference's hsi_* examples (QRNN3D layers) -------------------------------------------
+GRUNET_FORMS = {"k3": 0, "down": 1, "k1": 2, "up": 3}
+GRUNET_MODES = {"f16x2": 3, "bf16x3": 6}
+
+
+def grunet_layer_table(in_ch=2):
+    """The 34 layers of ``GRUnet(in_ch, 1, bn=False)`` in the reference's state-dict order (grunet.py:41-67), each as
+    ``(key, form, cin, hidden, direction, transposed, level)``: ``key`` the reference's weight key, ``form`` a key of GRUNET_FORMS,
+    ``direction`` "fwd" / "rev" / "bi" (3 * hidden gate channels instead of 2), ``level`` the OUTPUT plane (H / 2^level)."""
+    T = [(f"Down{l + 1}.conv.conv.weight", "down", 16 << l, 16 << l, "rev", False, l + 1) for l in range(4)]
+    T.append(("Conv1.conv.conv.weight", "k3", in_ch, 16, "bi", False, 0))
+    for l in range(4):
+        ci, co = 16 << l, 32 << l
+        T += [(f"Conv{l + 2}.conv1.conv.conv.weight", "k3", ci, co, "fwd", False, l + 1),
+              (f"Conv{l + 2}.conv2.conv.conv.weight", "k3", co, co, "fwd", False, l + 1),
+              (f"Conv{l + 2}.conv_residual.conv.conv.weight", "k1", ci, co, "fwd", False, l + 1)]
+    for l in range(4):
+        ci, co, n = 256 >> l, 128 >> l, 5 - l
+        T += [(f"Up{n}.conv.upsample_conv.conv3d.weight", "up", ci, co, "rev", False, 3 - l),
+              (f"Up_conv{n}.conv1.conv.deconv.weight", "k3", ci, co, "fwd", True, 3 - l),
+              (f"Up_conv{n}.conv2.conv.deconv.weight", "k3", co, co, "fwd", True, 3 - l),
+              (f"Up_conv{n}.conv_residual.conv.deconv.weight", "k1", ci, co, "fwd", True, 3 - l)]
+    T.append(("Conv.conv.deconv.weight", "k3", 16, 1, "bi", True, 0))
+    return T
+
+
+def grunet_macs_per_voxel(in_ch=2):
+    """multiply-adds per full-resolution voxel, from the layer table (a layer of level l runs on 1 / 4^l of the voxels)"""
+    total = 0.0
+    for _, form, cin, hidden, direction, _, level in grunet_layer_table(in_ch):
+        total += (1 if form == "k1" else 27) * cin * hidden * (3 if direction == "bi" else 2) / 4.0 ** level
+    return total
+
+
+class GRUnet(RefKeyed):
+    """``GRUnet(in_ch, 1, use_noise_map = in_ch == 2, bn=False)`` of the reference (models/qrnn/grunet.py; ``grunet_masked_nobn()`` is
+    ``in_ch=2``): a four-level U-Net of QRNN3D layers -- a 3-D gate convolution and f-pooling along the band axis.  The forward pass is
+    one ``dpx_grunet_forward`` call on the gfx950 kernels of dpx_qrnn3d.hip; the 35 parameters carry the reference's state-dict keys, so
+    its checkpoint (``checkpoint['net']``) loads with ``strict=True``.  Forward only: a call that autograd would have to
+    differentiate raises NotImplementedError.
+
+    ``compute_mode``: "f16x2" (split-f16, the default: operands inside the binary16 range, watched by the range trap of the FFDNet
+    layers) or "bf16x3" (split-bf16, any range); ``f16_fallback`` as for FFDNet."""
+
+    def __init__(self, in_ch=2, out_ch=1, use_noise_map=None, bn=False):
+        super().__init__()
+        if bn:
+            raise NotImplementedError("GRUnet(bn=True) -- the batch-norm checkpoints (grunet_masked, 205 keys) -- is not built for the HIP backend: "
+                                      "use the bn=False network (grunet_masked_nobn, unet_qrnn3d.pth)")
+        if in_ch not in (1, 2) or out_ch != 1:
+            raise ValueError(f"GRUnet: in_ch 1 or 2 and out_ch 1, got in_ch={in_ch} out_ch={out_ch}")
+        if use_noise_map is not None and bool(use_noise_map) != (in_ch == 2):
+            raise ValueError("GRUnet: use_noise_map goes with in_ch=2 (the cube and its noise map)")
+        self.in_ch = in_ch
+        self.table = grunet_layer_table(in_ch)
+        for key, form, cin, hidden, direction, tr, _ in self.table:
+            k, gates = (1 if form == "k1" else 3), hidden * (3 if direction == "bi" else 2)
+            self.add_ref_param(key, (cin, gates, k, k, k) if tr else (gates, cin, k, k, k), requires_grad=False)
+        self.add_ref_param("Conv.conv.deconv.bias", (3,), requires_grad=False)
+        self.compute_mode = os.environ.get("DPX_GRUNET_MODE", "f16x2")
+        self.f16_fallback = os.environ.get("DPX_F16_FALLBACK", "bf16x3")
+        self._packed_modes = None
+
+    def _weights_changed(self):
+        super()._weights_changed()
+        self._packed_modes = None
+
+    def load_reference_state_dict(self, sd):
+        if isinstance(sd, dict) and "net" in sd and not any(k in sd for k in self._ref_attr):
+            sd = sd["net"]                                   # the reference's checkpoint: {'net': state_dict, ...}
+        if len(sd) > 100:
+            raise NotImplementedError(f"GRUnet: a state dict of {len(sd)} tensors is a batch-norm variant (grunet_masked: 205 keys); only the "
+                                      "bn=False network (35 keys) is built")
+        self.load_state_dict(sd, strict=True)
+        return self
+
+    def _mode_id(self):
+        if self.compute_mode not in GRUNET_MODES:
+            raise ValueError(f"GRUnet.compute_mode: 'f16x2' or 'bf16x3', got {self.compute_mode!r}")
+        return GRUNET_MODES[self.compute_mode]
+
+    def packed(self, mode):
+        """the weights pre-split for the matrix cores (dpx_grunet_pack), cached per weight version, device and mode"""
+        dev = self.ref_param(self.table[0][0]).device
+        key = (self._weights_version(), str(dev), mode)
+        if self._packed_modes is None or self._packed_modes[0] != key:
+            L = be.lib()
+            blob = ops._bytes(L.query("dpx_grunet_packed_bytes", self.in_ch, mode), dev)
+            ws = [self.ref_param(k).detach().float().contiguous() for k, *_ in self.table]
+            bias = self.ref_param("Conv.conv.deconv.bias").detach().float().contiguous()
+            pw = (ctypes.c_void_p * len(ws))(*[w.data_ptr() for w in ws])
+            L.call("dpx_grunet_pack", be.ptr(blob), pw, be.ptr(bias), self.in_ch, mode, be.stream())
+            self._packed_modes = (key, blob)
+        return self._packed_modes[1]
+
+    def forward(self, x, sigma=None):
+        """x: [N, D, H, W] (D bands), sigma: 0-d or [N] (in_ch = 2) -> net(cat(x, sigma)) + x, [N, D, H, W]"""
+        if x.ndim != 4:
+            raise ValueError(f"GRUnet: a 4-D batch of cubes [N, bands, H, W], got shape {tuple(x.shape)}")
+        N, D, H, W = (int(s) for s in x.shape)
+        if H % 16 or W % 16:
+            raise ValueError(f"GRUnet: H and W must be multiples of 16 (four stride-2 levels whose skips are concatenated), got {H} x {W}")
+        if D < 1 or N < 1:
+            raise ValueError(f"GRUnet: at least one cube of at least one band, got shape {tuple(x.shape)}")
+        if (self.in_ch == 2) != (sigma is not None):
+            raise ValueError("GRUnet: sigma goes with in_ch=2")
+        if torch.is_grad_enabled() and (x.requires_grad or (isinstance(sigma, torch.Tensor) and sigma.requires_grad)
+                                        or any(p.requires_grad for p in self.parameters())):
+            raise NotImplementedError("GRUnet is forward-only: its backward pass is not built (call it under torch.no_grad(), on inputs "
+                                      "and weights that need no gradient)")
+        mode = self._mode_id()
+        be.require(x, what="GRUnet input")
+        sig = ops.as_batch_vec(sigma, N, x.device) if sigma is not None else None
+        L = be.lib()
+        if mode == 3:
+            be.note_f16_launch()
+        x = x.contiguous()
+        y = torch.empty_like(x)
+        ws = ops.workspace("grunet", L.query("dpx_grunet_ws_bytes", N, D, H, W), x.device)
+        L.call("dpx_grunet_forward", be.ptr(x), be.ptr(sig), be.ptr(y), be.ptr(self.packed(mode)), self.in_ch, mode, N, D, H, W, be.ptr(ws), be.stream())
+        return y
+
+
+def qrnn3d_models_not_built(name):
+    raise NotImplementedError(f"{name} is not built for the HIP backend: the reference's qrnn3d() / qrnn2d() / qrnn3d_masked() constructors do not run "
+                              "(models/qrnn/__init__.py binds QRNNREDC3D to None), so there is nothing to match; the hyperspectral denoiser is GRUNetDenoiser")
+
+
+class GRUNetDenoiser(Denoiser):
+    """reference denoisers/wrapper.py:172-192: ``grunet_masked_nobn()`` on the cube as one channel and sigma repeated as the second;
+    ``[N, B, H, W]`` with sigma 0-d or ``[N]`` -> ``[N, B, H, W]``.  ``model_path``: the reference's checkpoint
+    (``pnp_denoisers/unet_qrnn3d.pth``, read as ``checkpoint['net']``), a ``{'net': state_dict}`` / state dict, or None (zero weights).
+    Extension over the reference: a single sigma for N > 1 cubes broadcasts (the reference fails in ``torch.cat``).  H and W are
+    multiples of 16 (ValueError otherwise, where the reference dies in ``torch.cat``).  Forward only."""
+
+    def __init__(self, model_path=None):
+        super().__init__()
+        self.model = _load_checkpoint(GRUnet(in_ch=2), model_path)
+        self.use_noise_map = True
+
+    def denoise(self, input, sigma):
+        if not isinstance(sigma, torch.Tensor):
+            sigma = torch.as_tensor(float(sigma))
+        return super().denoise(input, sigma)
+
+    def _denoise(self, x, sigma):
+        return self.model(x, sigma.reshape(-1))
+
+
+class GRUNetTVDenoiser(Denoiser):
+    def __init__(self, *a, **k):
+        raise NotImplementedError("GRUNetTVDenoiser (the mean of GRUNet and a TV denoiser at sigma * 255) is not built for the HIP backend: "
+                                  "compose GRUNetDenoiser and TVDenoiser yourself")
+
+
+class QRNN3DDenoiser(Denoiser):
+    def __init__(self, *a, **k):
+        qrnn3d_models_not_built("QRNN3DDenoiser")

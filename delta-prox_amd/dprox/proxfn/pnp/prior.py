@@ -9,7 +9,7 @@ import torch.nn as nn
 from ... import _ops as ops
 from ...utils import safe_sqrt
 from ..core import ProxFn
-from .denoisers import Augment, DRUNetDenoiser, FFDNetColorDenoiser, FFDNetDenoiser, IRCNNDenoiser, TVDenoiser, UNetDenoiser
+from .denoisers import Augment, DRUNetDenoiser, FFDNetColorDenoiser, FFDNetDenoiser, GRUNetDenoiser, IRCNNDenoiser, TVDenoiser, UNetDenoiser, qrnn3d_models_not_built
 
 CACHE_DIR = os.path.join(os.path.expanduser("~"), ".cache", "dprox")
 
@@ -22,7 +22,12 @@ def get_denoiser(type):
         return TVDenoiser(5, type.startswith("tv3d"), differentiable=type.endswith("_diff"))
     table = {"ffdnet": ("ffdnet_gray.pth", FFDNetDenoiser), "ffdnet_color": ("ffdnet_color.pth", FFDNetColorDenoiser),
              "drunet": ("drunet_gray.pth", lambda p: DRUNetDenoiser(1, p)), "drunet_color": ("drunet_color.pth", lambda p: DRUNetDenoiser(3, p)),
-             "ircnn": ("ircnn_gray.pth", lambda p: IRCNNDenoiser(1, p)), "unet": ("unet-nm.pt", UNetDenoiser)}
+             "ircnn": ("ircnn_gray.pth", lambda p: IRCNNDenoiser(1, p)), "unet": ("unet-nm.pt", UNetDenoiser), "grunet": ("unet_qrnn3d.pth", GRUNetDenoiser)}
+    if type in ("qrnn3d", "qrnn2d", "qrnn3d_masked"):
+        qrnn3d_models_not_built(f"denoiser {type!r}")
+    if type in ("grunet_tv", "grunet_masked"):
+        raise NotImplementedError(f"denoiser {type!r} is not built for the MI355X backend: of the GRUNet family only 'grunet' (grunet_masked_nobn, "
+                                  "unet_qrnn3d.pth) is")
     if type not in table:
         raise ValueError(f"denoiser {type!r} is not built for the MI355X backend (have {sorted(table) + ['tv', 'tv3d']}); "
                          "pass a Denoiser instance instead")

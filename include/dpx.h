@@ -876,6 +876,39 @@ int dpx_lp_pcg_iters(const void* const* tab, long m, long n, long nnz, double rh
 int dpx_lp_tail(const void* const* tab, long m, long n, long nnz, double alpha, double rho, dpx_stream_t stream);
 int dpx_lp_eval(const void* const* tab, long m, long n, long nnz, double gamma_c, double gamma_b, dpx_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------ */
+/* GRUNet (QRNN3D layers: a 3-D gate convolution + f-pooling along the band axis)              */
+/* ------------------------------------------------------------------------------------------ */
+/* The hyperspectral denoiser of the reference's hsi_* examples -- models/qrnn/grunet.py, layer.py, conv.py -- forward only
+ * (csrc/dpx_qrnn3d.hip).  A layer is a 3-D convolution to `gates` channels followed by the scan along D,
+ *   Z = tanh(gates[:C]),  F = sigmoid(gates[C:2C]):   h_0 = (1 - f_0) z_0,   h_d = f_d h_{d-1} + (1 - f_d) z_d
+ * direction 0: d upwards, 1: d downwards ("reverse"), 2: bidirectional -- 3 C gate channels Z, F1, F2, the sum of an upward scan with F1
+ * and a downward scan with F2.  form: 0 = Conv3d k 3 s 1 p 1, 1 = k 3 s (1, 2, 2) p 1, 2 = k 1, 3 = Upsample((1, 2, 2), trilinear,
+ * align_corners) + Conv3d k 3 p 1; a ConvTranspose3d (s 1; forms 0 and 2) is packed with transposed = 1 from its own [cin][cout][taps]
+ * tensor.  mode: 3 = split-f16 (operands inside the binary16 range: dpx_ffdnet_f16_overflow is the trap of these layers too), 6 =
+ * split-bf16 (any range); both are fp32-accurate, a blob is valid for the mode it was packed in.  Contiguous fp32 tensors, channels-first
+ * [N][C][D][H][W]; cin <= 256, gate channels <= 1024.
+ *   dpx_qrnn3d_pack     one layer's weights ([cout][cin][taps], cout = the GATE channels; bias [cout] or NULL) -> packed
+ *   dpx_qrnn3d_layer    out[:, out_offset : out_offset + hidden] = pool(conv(x)) + pool(conv_r(xr)): the second operand (cin_r = 0:
+ *                       none) is another layer of the same hidden width and output plane on its own input, pooled in the same pass in
+ *                       the same direction -- a block's conv_residual branch.  out [N][out_channels][D][Ho][Wo].
+ *   dpx_grunet_*        GRUnet(in_ch, 1, use_noise_map = in_ch == 2, bn = False) whole: y = net(cat(x, sigma)) + x for x, y [N][D][H][W]
+ *                       (D bands), sigma [N] on the device; w: the 34 weight tensors in state-dict order, bias: Conv.conv.deconv.bias.
+ *                       H and W multiples of 16, any D >= 1.  Everything runs on the caller's workspace; torch.cat is a channel offset.
+ * Argument errors (a plane that is no multiple of 16, D < 1, an unknown mode or form) return DPX_ERR_ARG (the size queries: 0) and
+ * launch nothing.                                                                                                                */
+size_t dpx_qrnn3d_packed_bytes(int form, int cin, int cout, int mode);
+int dpx_qrnn3d_pack(void* packed, const float* w, const float* bias, int form, int cin, int cout, int transposed, int mode, dpx_stream_t stream);
+size_t dpx_qrnn3d_layer_ws_bytes(int form, int form_r, int N, int cin, int cin_r, int hidden, int direction, int D, int H, int W);
+int dpx_qrnn3d_layer(const float* x, const void* packed, const float* xr, const void* packed_r, float* out, int form, int form_r, int N, int cin,
+                     int cin_r, int hidden, int direction, int D, int H, int W, int out_channels, int out_offset, int mode, void* ws,
+                     dpx_stream_t stream);
+size_t dpx_grunet_packed_bytes(int in_ch, int mode);
+int dpx_grunet_pack(void* packed, const float* const* w, const float* bias, int in_ch, int mode, dpx_stream_t stream);
+size_t dpx_grunet_ws_bytes(int N, int D, int H, int W);
+int dpx_grunet_forward(const float* x, const float* sigma, float* y, const void* packed, int in_ch, int mode, int N, int D, int H, int W, void* ws,
+                       dpx_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
