@@ -1684,6 +1684,274 @@ int masked_normal_apply_fused(float* p, const float* r, float* Ap, float2* z, co
   return launch_status("masked_normal_apply_fused");
 }
 
+// ---------------------------------------------------------------------------------------------
+// the Fresnel propagator of the DOE model (dpx_doe.hip):  w_c = crop_RxR( F^-1( H_c . F( zero-pad_p(u_c) ) ) ),  M = R + 2 p
+// in the same three launches as the masked normal operator above, on a compact spectrum Z [3][R][M] -- only the R live rows of a
+// padded plane are ever transformed along the row axis (the 2 p zero rows transform to zeros, which the column kernel puts into
+// LDS itself), and only the R cropped rows leave the column kernel:
+//   k_doe_rows_in  : the field of a row, formed in the load and zero-padded in LDS -> row spectrum.  MODE 0: u = a exp(i k_c s^2)
+//                    from the height map's square root s (full-range sincosf; the complex field never exists in memory), MODE 1:
+//                    an explicit complex field (times the aperture a or not), MODE 2: the backward pass's
+//                    g_w = 2 (g - <g, psf>) / (f^2 sum q) w on the f x f block of every psf pixel
+//   k_doe_cols     : column transform -> . H_c (CONJ: its conjugate; H carries the 1 / M^2 of the inverse transforms) -> inverse
+//                    column transform, the column resident in LDS, in place
+//   k_doe_rows_out : inverse row transform -> crop -> w (optional) and q = f x f block mean of |w|^2 with the sum of q over the
+//                    launch (per-workgroup partials in float64, added by the last workgroup: dpx_reduce_dev.h)
+//   k_doe_rows_grad: the backward pass's last kernel -- the rows of all three channels of g_u in one workgroup, so that
+//                    g_s = 2 s sum_c k_c Im(conj(u_c) g_u_c) is one store per pixel (no atomics); u_c is recomputed from s
+// The aperture is the exact integer rule (2 i - (R - 1))^2 + (2 j - (R - 1))^2 < (R - 1)^2.
+// ---------------------------------------------------------------------------------------------
+__device__ __forceinline__ bool doe_aperture(int i, int j, int R) {
+  const long long a = 2 * i - (R - 1), b = 2 * j - (R - 1), r = R - 1;
+  return a * a + b * b < r * r;
+}
+struct DoeRowsIn {
+  const float* s;          // MODE 0: [R][R]
+  const float2* field;     // MODE 1: the field, MODE 2: the forward pass's w; [3][R][R]
+  const float* g;          // MODE 2: cotangent of the psf [3][P][P]
+  const double* stat;      // MODE 2: stat[0] = sum q, stat[1] = <g, psf>
+  float kc[3];             // MODE 0: (2 pi / lambda_c)(n_c - 1)
+  int aperture;            // MODE 1: multiply by the aperture
+  int f, P;                // MODE 2
+};
+
+template <int MODE>
+__global__ void k_doe_rows_in(DoeRowsIn A, float2* __restrict__ Z, int R, int p, Plan1D plan, const float2* __restrict__ tw, int rpb) {
+  HIP_DYNAMIC_SHARED(float2, smem)
+  const int M = R + 2 * p, ld = M + 1;
+  float2* a = smem;
+  float2* b = smem + rpb * ld;
+  const int tid = threadIdx.x, nthr = blockDim.x;
+  const int row0 = blockIdx.x * rpb;
+  const int nseq = min(rpb, 3 * R - row0);
+  double gscale = 0.0, dot = 0.0;
+  if (MODE == 2) {
+    gscale = 2.0 / ((double)A.f * A.f * A.stat[0]);
+    dot = A.stat[1];
+  }
+  for (int e = tid; e < nseq * M; e += nthr) {
+    const int sq = e / M, n = e - sq * M, j = n - p;
+    const int gr = row0 + sq, c = gr / R, i = gr - c * R;
+    float2 v = make_float2(0.f, 0.f);
+    if (j >= 0 && j < R) {
+      if (MODE == 0) {
+        if (doe_aperture(i, j, R)) {
+          const float sv = A.s[(size_t)i * R + j];
+          sincosf((c == 0 ? A.kc[0] : c == 1 ? A.kc[1] : A.kc[2]) * (sv * sv), &v.y, &v.x);
+        }
+      } else if (MODE == 1) {
+        if (!A.aperture || doe_aperture(i, j, R)) v = A.field[(size_t)gr * R + j];
+      } else {
+        const float gq = (float)(((double)A.g[((size_t)c * A.P + i / A.f) * A.P + j / A.f] - dot) * gscale);
+        v = cscale(A.field[(size_t)gr * R + j], gq);
+      }
+    }
+    a[sq * ld + n] = v;
+  }
+  __syncthreads();
+  const Twid<float2> twd{tw, M};
+  const float2* z = fft_lds<-1, float2>(a, b, plan, twd, 1, nseq, ld, tid, nthr);
+  for (int e = tid; e < nseq * M; e += nthr) {
+    const int sq = e / M, k = e - sq * M;
+    Z[(size_t)(row0 + sq) * M + k] = z[sq * ld + k];
+  }
+}
+
+template <bool CONJ>
+__global__ void __launch_bounds__(512) k_doe_cols(float2* __restrict__ Z, const float2* __restrict__ Hc, int R, int p, Plan1D plan,
+                                                  const float2* __restrict__ tw, int CT) {
+  HIP_DYNAMIC_SHARED(float2, smem)
+  const int M = R + 2 * p, ld = M + 1;
+  float2* a = smem;
+  float2* b = smem + CT * ld;
+  const int tid = threadIdx.x, nthr = blockDim.x;
+  const int c = blockIdx.y, l0 = blockIdx.x * CT;
+  const int nseq = min(CT, M - l0);
+  float2* base = Z + (size_t)c * R * M;
+  const float2* Hb = Hc + (size_t)c * M * M;
+  for (int e = tid; e < M * nseq; e += nthr) {
+    const int r = e / nseq, cc = e - r * nseq, i = r - p;
+    a[cc * ld + r] = (i >= 0 && i < R) ? base[(size_t)i * M + l0 + cc] : make_float2(0.f, 0.f);
+  }
+  __syncthreads();
+  const Twid<float2> twd{tw, M};
+  float2* z = fft_lds<-1, float2>(a, b, plan, twd, 1, nseq, ld, tid, nthr);
+  for (int e = tid; e < M * nseq; e += nthr) {
+    const int k = e / nseq, cc = e - k * nseq;
+    const float2 h = Hb[(size_t)k * M + l0 + cc];
+    z[cc * ld + k] = CONJ ? cmulc(z[cc * ld + k], h) : cmul(z[cc * ld + k], h);
+  }
+  __syncthreads();
+  const float2* y = fft_lds<+1, float2>(z, z == a ? b : a, plan, twd, 1, nseq, ld, tid, nthr);
+  for (int e = tid; e < R * nseq; e += nthr) {
+    const int i = e / nseq, cc = e - i * nseq;
+    base[(size_t)i * M + l0 + cc] = y[cc * ld + p + i];
+  }
+}
+
+// rows: a multiple of f that divides R (a workgroup's rows are whole block rows of one channel).  q == NULL: only w is written
+// (the propagator on its own); w == NULL: no field is kept (no gradient is needed)
+__global__ void k_doe_rows_out(const float2* __restrict__ Z, float2* __restrict__ w, float* __restrict__ q, int R, int p, int f, Plan1D plan,
+                               const float2* __restrict__ tw, int rows, double* __restrict__ partial, unsigned* __restrict__ counter,
+                               double* __restrict__ stat) {
+  HIP_DYNAMIC_SHARED(float2, smem)
+  __shared__ double shred[16];
+  __shared__ int shlast;
+  const int M = R + 2 * p, ld = M + 1, P = R / f;
+  float2* a = smem;
+  float2* b = smem + rows * ld;
+  const int tid = threadIdx.x, nthr = blockDim.x;
+  const int row0 = blockIdx.x * rows;                    // of 3 R
+  for (int e = tid; e < rows * M; e += nthr) {
+    const int sq = e / M, n = e - sq * M;
+    a[sq * ld + n] = Z[(size_t)(row0 + sq) * M + n];
+  }
+  __syncthreads();
+  const Twid<float2> twd{tw, M};
+  const float2* z = fft_lds<+1, float2>(a, b, plan, twd, 1, rows, ld, tid, nthr);
+  if (w)
+    for (int e = tid; e < rows * R; e += nthr) {
+      const int sq = e / R, j = e - sq * R;
+      w[(size_t)(row0 + sq) * R + j] = z[sq * ld + p + j];
+    }
+  if (!q) return;
+  const float inv = 1.0f / (float)(f * f);
+  double acc = 0.0;
+  for (int e = tid; e < (rows / f) * P; e += nthr) {
+    const int br = e / P, X = e - br * P;
+    float t = 0.f;
+    for (int dy = 0; dy < f; ++dy)
+      for (int dx = 0; dx < f; ++dx) {
+        const float2 v = z[(br * f + dy) * ld + p + X * f + dx];
+        t = fmaf(v.x, v.x, fmaf(v.y, v.y, t));
+      }
+    t *= inv;
+    q[(size_t)(row0 / f + br) * P + X] = t;               // (row0 / f counts block rows over the three channels: R / f = P per channel)
+    acc += (double)t;
+  }
+  acc = block_sum(acc, shred);
+  if (tid == 0) dpx_st_agent(partial + blockIdx.x, acc);
+  if (!dpx_last_block(counter, gridDim.x, &shlast)) return;
+  if (tid < 64) {
+    const double S = sum_partials_f64(partial, (int)gridDim.x);
+    if (tid == 0) stat[0] = S;
+  }
+}
+
+__global__ void k_doe_rows_grad(const float2* __restrict__ Z, const float* __restrict__ s, float* __restrict__ gs, float kc0, float kc1, float kc2,
+                                int R, int p, Plan1D plan, const float2* __restrict__ tw, int rows) {
+  HIP_DYNAMIC_SHARED(float2, smem)
+  const int M = R + 2 * p, ld = M + 1;
+  float2* a = smem;
+  float2* b = smem + 3 * rows * ld;
+  const int tid = threadIdx.x, nthr = blockDim.x;
+  const int i0 = blockIdx.x * rows;
+  const int nr = min(rows, R - i0), nseq = 3 * nr;          // sequence 3 rr + c = row i0 + rr of channel c
+  for (int e = tid; e < nseq * M; e += nthr) {
+    const int sq = e / M, n = e - sq * M, rr = sq / 3, c = sq - 3 * rr;
+    a[sq * ld + n] = Z[((size_t)c * R + i0 + rr) * M + n];
+  }
+  __syncthreads();
+  const Twid<float2> twd{tw, M};
+  const float2* z = fft_lds<+1, float2>(a, b, plan, twd, 1, nseq, ld, tid, nthr);
+  const float kc[3] = {kc0, kc1, kc2};
+  for (int e = tid; e < nr * R; e += nthr) {
+    const int rr = e / R, j = e - rr * R, i = i0 + rr;
+    float out = 0.f;
+    if (doe_aperture(i, j, R)) {
+      const float sv = s[(size_t)i * R + j], h = sv * sv;
+      float t = 0.f;
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        float sn, cs;
+        sincosf(kc[c] * h, &sn, &cs);
+        const float2 gu = z[(3 * rr + c) * ld + p + j];
+        t = fmaf(kc[c], fmaf(cs, gu.y, -sn * gu.x), t);       // k_c Im(conj(u_c) g_u_c)
+      }
+      out = 2.f * sv * t;
+    }
+    gs[(size_t)i * R + j] = out;
+  }
+}
+
+// launch geometry of the four kernels for a wavefront of R x R samples averaged over f x f blocks: everything has to fit a CU's LDS
+struct DoeGeom {
+  int M, p, rpb_in, rows_out, rows_grad, ct_max;
+  size_t sh_in, sh_out, sh_grad;
+  bool ok;
+};
+static DoeGeom doe_geom(int R, int f) {
+  DoeGeom g{};
+  g.p = R / 4;
+  g.M = R + 2 * g.p;
+  const int base = lds_geom(g.M, g.M).rpb;               // rows of a 4096-point workgroup (1 .. 16)
+  g.rpb_in = base;
+  const int P = R / f;
+  int k = 1;                                             // block rows per workgroup: a divisor of P
+  for (int t = 2; t <= P && f * t <= base; ++t)
+    if (P % t == 0) k = t;
+  g.rows_out = f * k;
+  g.rows_grad = base / 3 > 0 ? base / 3 : 1;
+  g.ct_max = (int)(LDS_CU_BYTES / lds_seq_bytes(1, g.M));
+  if (g.ct_max > 16) g.ct_max = 16;
+  g.sh_in = lds_seq_bytes(g.rpb_in, g.M);
+  g.sh_out = lds_seq_bytes(g.rows_out, g.M);
+  g.sh_grad = lds_seq_bytes(3 * g.rows_grad, g.M);
+  g.ok = g.ct_max >= 1 && g.sh_in <= LDS_CU_BYTES && g.sh_out <= LDS_CU_BYTES && g.sh_grad <= LDS_CU_BYTES;
+  return g;
+}
+bool doe_fits(int R, int f) { return R >= 4 && f >= 1 && R % f == 0 && doe_geom(R, f).ok; }
+int doe_cols_widest(int R) { return doe_geom(R, 1).ct_max; }
+// columns per workgroup the library ships: ONE.  Measured on an MI355X (profiles/doe_bench.json): the column launch takes 0.79 ms with one
+// column per workgroup and 1.08 ms with the widest tile a CU's LDS holds (4 columns, 144 KB) at M = 2244, 0.21 against 0.34 ms (9 columns)
+// at M = 1122 -- a wide tile's 32-byte pieces do not pay for one resident workgroup per CU.  Wider tiles stay available (cols_per_wg).
+int doe_cols_default(int R) { return doe_geom(R, 1).ct_max >= 1 ? 1 : 0; }
+int doe_rows_out_blocks(int R, int f) { return 3 * R / doe_geom(R, f).rows_out; }
+
+int doe_rows_in(int mode, const float* sq, const float2* field, const float* g, const double* stat, const float* kc, int aperture, float2* Z, int R,
+                int f, const void* table, hipStream_t s) {
+  const DoeGeom G = doe_geom(R, f);
+  const Plan1D plan = make_plan(G.M);
+  DoeRowsIn A{sq, field, g, stat, {kc ? kc[0] : 0.f, kc ? kc[1] : 0.f, kc ? kc[2] : 0.f}, aperture, f, R / f};
+  const dim3 grid((3 * R + G.rpb_in - 1) / G.rpb_in);
+  if (mode == 0)
+    DPX_LAUNCH_LDS("k_doe_rows_in", k_doe_rows_in<0>, grid, dim3(256), G.sh_in, s, A, Z, R, G.p, plan, tw_rows(table), G.rpb_in);
+  else if (mode == 1)
+    DPX_LAUNCH_LDS("k_doe_rows_in", k_doe_rows_in<1>, grid, dim3(256), G.sh_in, s, A, Z, R, G.p, plan, tw_rows(table), G.rpb_in);
+  else
+    DPX_LAUNCH_LDS("k_doe_rows_in", k_doe_rows_in<2>, grid, dim3(256), G.sh_in, s, A, Z, R, G.p, plan, tw_rows(table), G.rpb_in);
+  return launch_status("doe_rows_in");
+}
+
+int doe_cols(float2* Z, const float2* H, int conj, int R, int ct, const void* table, hipStream_t s) {
+  const DoeGeom G = doe_geom(R, 1);
+  const Plan1D plan = make_plan(G.M);
+  const dim3 grid((G.M + ct - 1) / ct, 3), block((long)ct * G.M > 2048 ? 512 : 256);
+  const size_t sh = lds_seq_bytes(ct, G.M);
+  if (conj)
+    DPX_LAUNCH_LDS("k_doe_cols", k_doe_cols<true>, grid, block, sh, s, Z, H, R, G.p, plan, tw_rows(table), ct);
+  else
+    DPX_LAUNCH_LDS("k_doe_cols", k_doe_cols<false>, grid, block, sh, s, Z, H, R, G.p, plan, tw_rows(table), ct);
+  return launch_status("doe_cols");
+}
+
+int doe_rows_out(const float2* Z, float2* w, float* q, double* partial, unsigned* counter, double* stat, int R, int f, const void* table,
+                 hipStream_t s) {
+  const DoeGeom G = doe_geom(R, f);
+  const Plan1D plan = make_plan(G.M);
+  DPX_LAUNCH_LDS("k_doe_rows_out", k_doe_rows_out, dim3(3 * R / G.rows_out), dim3(256), G.sh_out, s, Z, w, q, R, G.p, f, plan, tw_rows(table),
+                 G.rows_out, partial, counter, stat);
+  return launch_status("doe_rows_out");
+}
+
+int doe_rows_grad(const float2* Z, const float* sq, float* gs, const float* kc, int R, const void* table, hipStream_t s) {
+  const DoeGeom G = doe_geom(R, 1);
+  const Plan1D plan = make_plan(G.M);
+  DPX_LAUNCH_LDS("k_doe_rows_grad", k_doe_rows_grad, dim3((R + G.rows_grad - 1) / G.rows_grad), dim3(256), G.sh_grad, s, Z, sq, gs, kc[0], kc[1],
+                 kc[2], R, G.p, plan, tw_rows(table), G.rows_grad);
+  return launch_status("doe_rows_grad");
+}
+
 }  // namespace dpx
 
 // ---------------------------------------------------------------------------------------------

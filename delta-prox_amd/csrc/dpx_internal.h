@@ -66,6 +66,25 @@ size_t masked_normal_fused_ws_floats(int B, int H, int W);      // (one partial 
 int masked_normal_apply_fused(float* p, const float* r, float* Ap, float2* z, const float* mask, int mask_images, const float* rho, float c,
                               float* state, float* dotws, unsigned* counter, int B, int H, int W, const void* table, hipStream_t s);
 
+// ---- dpx_fft.hip: the Fresnel propagator of the DOE model (dpx_doe.hip), w = crop(F^-1(H . F(zero-pad(u)))) -----------------
+// A wavefront of R x R samples padded by R / 4 on every side, three wavelengths, on a compact spectrum Z [3][R][R + 2 (R / 4)] complex.
+bool doe_fits(int R, int f);                // every kernel's workgroup fits a CU's LDS (f: side of the psf's averaging block, divides R)
+int doe_cols_widest(int R);                 // the most columns a column workgroup holds
+int doe_cols_default(int R);                // ... and the number the library launches with (one: measured)
+int doe_rows_out_blocks(int R, int f);      // workgroups of doe_rows_out = partial sums it hands to its last workgroup
+// mode 0: u_c = a exp(i kc[c] sq^2) from the height map's square root sq [R][R]; 1: `field` [3][R][R] (times the aperture a if asked);
+// 2: the backward pass's g_w from field = w, the psf's cotangent g [3][R / f][R / f] and stat = (sum q, <g, psf>).  kc: host, 3 values
+int doe_rows_in(int mode, const float* sq, const float2* field, const float* g, const double* stat, const float* kc, int aperture, float2* Z, int R,
+                int f, const void* table, hipStream_t s);
+// H: [3][M][M] with the inverse transforms' 1 / M^2 folded in; conj: multiply by its conjugate; ct: columns per workgroup
+int doe_cols(float2* Z, const float2* H, int conj, int R, int ct, const void* table, hipStream_t s);
+// w [3][R][R] (nullable) = the propagated field; q [3][R / f][R / f] (nullable) = block mean of |w|^2, stat[0] = its sum (partial:
+// doe_rows_out_blocks doubles, counter: one zeroed ticket)
+int doe_rows_out(const float2* Z, float2* w, float* q, double* partial, unsigned* counter, double* stat, int R, int f, const void* table,
+                 hipStream_t s);
+// gs [R][R] = 2 sq sum_c kc[c] Im(conj(u_c) g_u_c) on the aperture, 0 outside
+int doe_rows_grad(const float2* Z, const float* sq, float* gs, const float* kc, int R, const void* table, hipStream_t s);
+
 // ---- dpx_fft_pow2.hip: transforms of the power-of-two planes (pow2_path_available) -------------------------
 size_t pow2_spec_elems(int P, int H, int W);
 int seed_rows_pow2(const dpx_term* terms, int nterms, const float* rho, const float* x0, float2* spec, int B, int C, int H, int W, const void* table,

@@ -264,6 +264,16 @@ SIGNATURES = {
     "dpx_grunet_pack": (c_int, [c_void_p, POINTER(c_void_p), c_void_p, c_int, c_int, c_void_p]),
     "dpx_grunet_ws_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
     "dpx_grunet_forward": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "dpx_doe_propagator_bytes": (c_size_t, [c_int]),
+    "dpx_doe_propagator_init": (c_int, [c_void_p, c_int, c_double, c_double, POINTER(c_double), c_void_p]),
+    "dpx_doe_ws_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "dpx_doe_cols_per_wg": (c_int, [c_int, c_int]),
+    "dpx_doe_psf": (c_int, [c_void_p, c_void_p, POINTER(c_double), POINTER(c_double), c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
+                            c_void_p, c_void_p]),
+    "dpx_doe_psf_backward": (c_int, [c_void_p, c_void_p, c_void_p, POINTER(c_double), POINTER(c_double), c_void_p, c_void_p, c_void_p, c_int, c_int,
+                                     c_int, c_void_p, c_void_p]),
+    "dpx_doe_propagate": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
+    "dpx_doe_phase": (c_int, [c_void_p, c_int, POINTER(c_double), POINTER(c_double), c_void_p, c_long, c_void_p]),
 }
 
 

@@ -68,6 +68,7 @@ def clear_caches():
     _workspaces.clear()
     _psf_dev.clear()
     _dd_cache.clear()
+    _doe_contexts.clear()
 
 
 def _shape4(x):
@@ -1474,3 +1475,143 @@ def cs_xupdate(bs, y, mask, lam, num_psi):
     if needs_grad:
         return _CSXUpdateFn.apply(y, mask, lam if isinstance(lam, torch.Tensor) else None, y3, mask4, lam_vec, int(num_psi), *bs)
     return _cs_forward([b.detach() for b in bs], y3, mask4, lam_vec, int(num_psi))
+
+
+# ----------------------------------------------------------------------------------------------
+# DOE wave-optics model: height map -> psf (dpx_doe_psf / dpx_doe_psf_backward, csrc/dpx_doe.hip + the transform kernels of dpx_fft.hip)
+# ----------------------------------------------------------------------------------------------
+_doe_contexts = {}
+
+
+def _three_doubles(v, what):
+    """the three wavelengths' constants as host doubles: a float32 tensor's values widened exactly"""
+    vals = [float(x) for x in (v.detach().double().reshape(-1).tolist() if isinstance(v, torch.Tensor) else np.asarray(v, dtype=np.float64).reshape(-1))]
+    if len(vals) != 3:
+        raise NotImplementedError(f"DOE model: {len(vals)} {what} (three wavelengths are built: the reference's propagator is written for three)")
+    return (c_double * 3)(*vals)
+
+
+class DoeContext:
+    """what the DOE kernels need besides the height map, per (geometry, optics, device): the propagator's transfer function H
+    ([1, 3, M, M] complex64 with the inverse transforms' 1 / M^2 folded in, dpx_doe_propagator_init), the twiddle table of the M-point
+    transforms, the optical constants as host doubles, and the scratch workspace of calls that need no gradient"""
+
+    def __init__(self, R, P, distance, interval, wave_lengths, refractive_idcs, device):
+        self.R, self.P, self.M = int(R), int(P), int(R) + 2 * (int(R) // 4)
+        self.device = torch.device(device)
+        self.wl, self.ri = _three_doubles(wave_lengths, "wave lengths"), _three_doubles(refractive_idcs, "refractive indices")
+        self.distance, self.interval = float(distance), float(interval)
+        L = be.lib()
+        if self.R < 4 or self.P < 1 or self.R % self.P:
+            raise NotImplementedError(f"DOE model: a wavefront of {R} samples and a patch of {P} (the patch size must divide the wave resolution)")
+        if not L.query("dpx_doe_ws_bytes", self.R, self.P, 0):
+            raise NotImplementedError(f"DOE model: wave resolution {R} -> patch {P}: a padded row of {self.M} samples (times the {self.R // self.P} rows "
+                                      "of a block) is beyond the LDS-resident transforms")
+        self.table = fft_table(self.M, self.M, self.device)
+        nb = L.query("dpx_doe_propagator_bytes", self.R)
+        self.H = _bytes(nb, self.device)[:nb].view(torch.complex64).view(1, 3, self.M, self.M)
+        L.call("dpx_doe_propagator_init", ptr(self.H), self.R, c_double(self.distance), c_double(self.interval), self.wl, be.stream())
+        self.cols_per_wg = 0            # 0 = the library's choice (tools/bench_doe.py times the others)
+        self.last_ws_bytes = 0          # workspace of the most recent dpx_doe_psf call (a call that needs no gradient keeps no field)
+
+    def ws_bytes(self, keep_field):
+        return be.lib().query("dpx_doe_ws_bytes", self.R, self.P, int(bool(keep_field)))
+
+
+def doe_context(R, P, distance, interval, wave_lengths, refractive_idcs, device):
+    wl, ri = _three_doubles(wave_lengths, "wave lengths"), _three_doubles(refractive_idcs, "refractive indices")
+    key = (int(R), int(P), float(distance), float(interval), tuple(wl), tuple(ri), str(torch.device(device)))
+    c = _doe_contexts.get(key)
+    if c is None:
+        c = _doe_contexts[key] = DoeContext(R, P, distance, interval, wave_lengths, refractive_idcs, device)
+    return c
+
+
+def _doe_forward(doe, s, profile, keep_field):
+    """one dpx_doe_psf call on checked operands: (psf [1, 3, P, P], the workspace -- the caller's to keep when it holds the field)"""
+    L = be.lib()
+    nb = doe.ws_bytes(keep_field)
+    ws = _bytes(nb, doe.device) if keep_field else workspace("doe", nb, doe.device)
+    psf = torch.empty(1, 3, doe.P, doe.P, dtype=torch.float32, device=doe.device)
+    L.call("dpx_doe_psf", ptr(s), ptr(profile), doe.wl, doe.ri, ptr(psf), ptr(doe.H), ptr(doe.table), doe.R, doe.P, int(keep_field), doe.cols_per_wg,
+           ptr(ws), be.stream())
+    doe.last_ws_bytes = nb
+    return psf, ws
+
+
+class _DoePsfFn(torch.autograd.Function):
+    """ops.doe_psf under autograd: the forward keeps the propagated field in a workspace of its own, dpx_doe_psf_backward reads it"""
+
+    @staticmethod
+    def forward(ctx, s, doe):
+        sd = s.detach()
+        psf, ws = _doe_forward(doe, sd, None, True)
+        ctx.doe, ctx.ws = doe, ws
+        ctx.save_for_backward(sd, psf)
+        return psf
+
+    @staticmethod
+    def backward(ctx, g):
+        s, psf = ctx.saved_tensors
+        doe = ctx.doe
+        g = require(g.contiguous(), what="doe_psf cotangent")
+        gs = torch.empty_like(s)
+        be.lib().call("dpx_doe_psf_backward", ptr(g), ptr(psf), ptr(s), doe.wl, doe.ri, ptr(gs), ptr(doe.H), ptr(doe.table), doe.R, doe.P,
+                      doe.cols_per_wg, ptr(ctx.ws), be.stream())
+        return gs, None
+
+
+def _doe_check(t, doe, channels, dtype, what):
+    if not isinstance(t, torch.Tensor):
+        raise be.DpxError(f"{what}: expected a torch.Tensor, got {type(t)}")
+    if t.dtype != dtype:
+        raise NotImplementedError(f"{what}: {t.dtype} ({dtype} is built; no float64 or bf16 form of the DOE kernels)")
+    if tuple(t.shape) != (1, channels, doe.R, doe.R):
+        raise ValueError(f"{what}: shape {tuple(t.shape)}, expected {(1, channels, doe.R, doe.R)}")
+    return require(t.contiguous(), dtype=dtype, what=what)
+
+
+def doe_psf(doe, s):
+    """psf [1, 3, P, P] of the height map s^2 for s = height_map_sqrt [1, 1, R, R] fp32 (RGBCollimator.get_psf of the reference): three
+    transform launches + one normalising launch; differentiable in s (dpx_doe_psf_backward).  A call that needs no gradient keeps no
+    field."""
+    s = _doe_check(s, doe, 1, torch.float32, "doe_psf height_map_sqrt")
+    if torch.is_grad_enabled() and s.requires_grad:
+        return _DoePsfFn.apply(s, doe)
+    return _doe_forward(doe, s.detach(), None, False)[0]
+
+
+def doe_psf_from_profile(doe, phase_profile):
+    """the same psf from an explicit complex64 phase profile [1, 3, R, R] (multiplied by the aperture); forward only"""
+    if isinstance(phase_profile, torch.Tensor) and phase_profile.requires_grad and torch.is_grad_enabled():
+        raise NotImplementedError("doe_psf: the gradient with respect to an explicit phase_profile is not built (train height_map_sqrt, or "
+                                  "detach the profile)")
+    prof = _doe_check(phase_profile, doe, 3, torch.complex64, "doe_psf phase_profile")
+    return _doe_forward(doe, None, prof.detach(), False)[0]
+
+
+def doe_propagate(doe, field):
+    """crop(ifft2(fft2(zero-pad(field)) . H)) of a complex64 field [1, 3, R, R] (FresnelPropagator.forward of the reference); forward only"""
+    if isinstance(field, torch.Tensor) and field.requires_grad and torch.is_grad_enabled():
+        raise NotImplementedError("FresnelPropagator: the gradient with respect to an explicit field is not built")
+    field = _doe_check(field, doe, 3, torch.complex64, "doe_propagate field").detach()
+    out = torch.empty_like(field)
+    L = be.lib()
+    ws = workspace("doe", L.query("dpx_doe_ws_bytes", doe.R, doe.R, 0), doe.device)
+    L.call("dpx_doe_propagate", ptr(field), ptr(out), ptr(doe.H), ptr(doe.table), doe.R, doe.cols_per_wg, ptr(ws), be.stream())
+    return out
+
+
+def doe_phase(x, squared, wave_lengths, refractive_idcs):
+    """exp(i k_c h) as complex64 [1, 3, H, W] for h = x^2 (squared) or x, x fp32 with H W elements ([H, W] .. [1, 1, H, W]); forward only"""
+    if not isinstance(x, torch.Tensor):
+        raise be.DpxError(f"doe_phase: expected a torch.Tensor, got {type(x)}")
+    if x.dtype != torch.float32:
+        raise NotImplementedError(f"doe_phase: {x.dtype} (float32 is built)")
+    if x.ndim < 2 or x.numel() != int(x.shape[-2]) * int(x.shape[-1]) or x.numel() < 1:
+        raise ValueError(f"doe_phase: a height map of shape {tuple(x.shape)} (one plane: [H, W] .. [1, 1, H, W])")
+    wl, ri = _three_doubles(wave_lengths, "wave lengths"), _three_doubles(refractive_idcs, "refractive indices")
+    x = require(x.detach().contiguous(), what="doe_phase height map")
+    out = torch.empty(1, 3, int(x.shape[-2]), int(x.shape[-1]), dtype=torch.complex64, device=x.device)
+    be.lib().call("dpx_doe_phase", ptr(x), int(bool(squared)), wl, ri, ptr(out), x.numel(), be.stream())
+    return out

@@ -909,6 +909,41 @@ size_t dpx_grunet_ws_bytes(int N, int D, int H, int W);
 int dpx_grunet_forward(const float* x, const float* sigma, float* y, const void* packed, int in_ch, int mode, int N, int D, int H, int W, void* ws,
                        dpx_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------ */
+/* DOE wave-optics model: height map -> point spread function (contrib.optic)                 */
+/* ------------------------------------------------------------------------------------------ */
+/* RGBCollimator.get_psf of the reference (contrib/optic/doe_model.py, common.py) and its gradient (csrc/dpx_doe.hip, the transform
+ * kernels in csrc/dpx_fft.hip).  Three wavelengths, a square wavefront of R x R samples, zero-padded by p = R / 4 on every side to
+ * M = R + 2 p, a psf of P x P pixels per wavelength (P divides R, f = R / P):
+ *   u_c = a exp(i k_c s^2),  k_c = (2 pi / lambda_c)(n_c - 1),  a = [(2 i - (R-1))^2 + (2 j - (R-1))^2 < (R-1)^2]
+ *   w_c = crop( ifft2( fft2( pad(u_c) ) . H_c ) ),  q_c = f x f block mean of |w_c|^2,  psf = q / sum_{c,y,x} q
+ * Contiguous fp32 / complex64 device tensors; wave_lengths, refractive_idcs: three HOST doubles each.  `table` is
+ * dpx_fft_table_init(M, M).  cols_per_wg: columns a workgroup of the column launch holds, 0 = the library's choice
+ * (dpx_doe_cols_per_wg(R, 0)), at most dpx_doe_cols_per_wg(R, 1).
+ *   dpx_doe_propagator_init  H [3][M][M] complex64 = exp(-i pi d lambda_c (fx_k^2 + fy_l^2)) / M^2, fx = ifftshift((arange(M) -
+ *                            (M - 1) / 2) / (interval M)), evaluated in float64
+ *   dpx_doe_ws_bytes         workspace of dpx_doe_psf; keep_field = 1: with room for the propagated field w [3][R][R] that
+ *                            dpx_doe_psf_backward reads (a forward pass that needs no gradient stores no field)
+ *   dpx_doe_psf              s [R][R] (height_map_sqrt), or phase_profile [3][R][R] complex64 != NULL in its place (s may then be
+ *                            NULL; keep_field must be 0) -> psf [3][P][P].  Three transform launches + one normalising launch.
+ *   dpx_doe_psf_backward     g [3][P][P] (cotangent of psf), the psf and the workspace of the dpx_doe_psf call with keep_field = 1
+ *                            -> gs [R][R].  A reduction + three transform launches; no floating-point atomics.
+ *   dpx_doe_propagate        out [3][R][R] = crop(ifft2(fft2(pad(field)) . H)) for a complex64 field [3][R][R] (FresnelPropagator);
+ *                            ws: dpx_doe_ws_bytes(R, R, 0)
+ *   dpx_doe_phase            out [3][n] complex64 = exp(i k_c h), h = x^2 (squared = 1) or x, for x [n] (HeightMap.get_phase_profile)
+ * Argument errors (P not dividing R, R < 4, a row beyond the LDS-resident transforms, null pointers) return DPX_ERR_ARG (the size
+ * queries: 0) and launch nothing.                                                                                                  */
+size_t dpx_doe_propagator_bytes(int R);
+int dpx_doe_propagator_init(void* H, int R, double distance, double sample_interval, const double* wave_lengths, dpx_stream_t stream);
+size_t dpx_doe_ws_bytes(int R, int P, int keep_field);
+int dpx_doe_cols_per_wg(int R, int widest);
+int dpx_doe_psf(const float* s, const void* phase_profile, const double* wave_lengths, const double* refractive_idcs, float* psf, const void* H,
+                const void* table, int R, int P, int keep_field, int cols_per_wg, void* ws, dpx_stream_t stream);
+int dpx_doe_psf_backward(const float* g, const float* psf, const float* s, const double* wave_lengths, const double* refractive_idcs, float* gs,
+                         const void* H, const void* table, int R, int P, int cols_per_wg, void* ws, dpx_stream_t stream);
+int dpx_doe_propagate(const void* field, void* out, const void* H, const void* table, int R, int cols_per_wg, void* ws, dpx_stream_t stream);
+int dpx_doe_phase(const float* x, int squared, const double* wave_lengths, const double* refractive_idcs, void* out, long n, dpx_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,42 @@
+"""-m gpu: the DOE wave-optics model on exact-size, poisoned, guarded workspaces (tests/guarded_alloc.py): the propagator's table H is
+exactly dpx_doe_propagator_bytes long, the workspace of a forward pass exactly dpx_doe_ws_bytes -- with the propagated field behind the
+spectrum when a gradient is needed, without it otherwise -- and both start as 0xFF, so a partial sum, a ticket or a field element
+that is read but was never written surfaces as NaN in the case's own comparison, and a write past either end fails here.
+
+Like tests/test_gpu_guard_cs.py this module sorts in front of tests/test_gpu_guarded.py, whose closing test counts every size query of
+the binding among the queries its guarded runs have asked: the runs here hand theirs to it."""
+import pytest
+import torch
+
+import guarded_alloc as ga
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda"
+
+
+@pytest.fixture(scope="module", autouse=True)
+def _hip_lib_loaded():
+    from dprox import _backend as be
+    assert torch.cuda.is_available()
+    assert not be.host_mode()
+    assert "libdpx_hip.so" in be.lib().path
+    yield
+
+
+import doe_cases as dc  # noqa: E402
+
+RUNS = dc.GUARDED_RUNS
+
+
+@pytest.mark.parametrize("name", list(RUNS))
+def test_guarded(monkeypatch, name):
+    import test_gpu_guarded                    # (the module pytest has collected: its SEEN is what its closing test reads)
+    fn, args, queries = RUNS[name]
+    with ga.guarded(monkeypatch, label=name) as g:
+        try:
+            fn(DEV, *args)
+            g.check()
+        finally:
+            test_gpu_guarded.SEEN.update(g.seen)
+    assert set(queries) <= g.seen
+    assert g.buffers > 0, "the case allocated no query-sized buffer: nothing was guarded"
