@@ -1698,12 +1698,23 @@ int masked_normal_apply_fused(float* p, const float* r, float* Ap, float2* z, co
 //   k_doe_rows_out : inverse row transform -> crop -> w (optional) and q = f x f block mean of |w|^2 with the sum of q over the
 //                    launch (per-workgroup partials in float64, added by the last workgroup: dpx_reduce_dev.h)
 //   k_doe_rows_grad: the backward pass's last kernel -- the rows of all three channels of g_u in one workgroup, so that
-//                    g_s = 2 s sum_c k_c Im(conj(u_c) g_u_c) is one store per pixel (no atomics); u_c is recomputed from s
-// The aperture is the exact integer rule (2 i - (R - 1))^2 + (2 j - (R - 1))^2 < (R - 1)^2.
+//                    g_s = 2 s sum_c k_c Im(conj(u_c) g_u_c) is one store per pixel (no atomics); u_c is recomputed from s.
+//                    FIELD: the cotangent g_u itself [3][R][R] (times the aperture the forward pass applied) in place of its
+//                    projection onto s -- the gradient to an explicit phase profile or field, dL/dRe + i dL/dIm
+// The aperture is the exact integer rule (2 i - (R - 1))^2 + (2 j - (R - 1))^2 < (R - 1)^2; the half-circular kind adds
+// 2 j - (R - 1) > 0 (the reference's yy > 0 is the COLUMN coordinate: the left half of every row is dark, the centre column of an
+// odd R included).
+// EX = the hybrid model's generalisation, a template parameter so that the base model's kernels stay the code they were:
+// u_c = a exp(i (k_c (s + eps)^2 + phi_c)) with an optional plane phi [3][R][R] and either aperture kind (MODE 0, rows_grad:
+// g_s = 2 (s + eps) sum_c ...), and one normalisation per channel (MODE 2: stat[2 c] = sum q_c, stat[2 c + 1] = <g_c, psf_c>).
 // ---------------------------------------------------------------------------------------------
 __device__ __forceinline__ bool doe_aperture(int i, int j, int R) {
   const long long a = 2 * i - (R - 1), b = 2 * j - (R - 1), r = R - 1;
   return a * a + b * b < r * r;
+}
+// kind 0: the disc, 1: its right half
+__device__ __forceinline__ bool doe_aperture(int i, int j, int R, int kind) {
+  return (kind == 0 || 2 * j - (R - 1) > 0) && doe_aperture(i, j, R);
 }
 struct DoeRowsIn {
   const float* s;          // MODE 0: [R][R]
@@ -1711,11 +1722,14 @@ struct DoeRowsIn {
   const float* g;          // MODE 2: cotangent of the psf [3][P][P]
   const double* stat;      // MODE 2: stat[0] = sum q, stat[1] = <g, psf>
   float kc[3];             // MODE 0: (2 pi / lambda_c)(n_c - 1)
-  int aperture;            // MODE 1: multiply by the aperture
+  int aperture;            // MODE 1: multiply by the aperture (0: no, 1 + kind: yes)
   int f, P;                // MODE 2
+  const float* phi;        // MODE 0, EX: [3][R][R] added to the phase, or NULL
+  float eps;               // MODE 0, EX: added to s
+  int kind;                // MODE 0, EX: aperture kind
 };
 
-template <int MODE>
+template <int MODE, bool EX>
 __global__ void k_doe_rows_in(DoeRowsIn A, float2* __restrict__ Z, int R, int p, Plan1D plan, const float2* __restrict__ tw, int rpb) {
   HIP_DYNAMIC_SHARED(float2, smem)
   const int M = R + 2 * p, ld = M + 1;
@@ -1724,25 +1738,43 @@ __global__ void k_doe_rows_in(DoeRowsIn A, float2* __restrict__ Z, int R, int p,
   const int tid = threadIdx.x, nthr = blockDim.x;
   const int row0 = blockIdx.x * rpb;
   const int nseq = min(rpb, 3 * R - row0);
-  double gscale = 0.0, dot = 0.0;
-  if (MODE == 2) {
+  double gscale = 0.0, dot = 0.0, gscale_c[3] = {0.0, 0.0, 0.0}, dot_c[3] = {0.0, 0.0, 0.0};
+  if (MODE == 2 && !EX) {
     gscale = 2.0 / ((double)A.f * A.f * A.stat[0]);
     dot = A.stat[1];
+  }
+  if (MODE == 2 && EX) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      gscale_c[c] = 2.0 / ((double)A.f * A.f * A.stat[2 * c]);
+      dot_c[c] = A.stat[2 * c + 1];
+    }
   }
   for (int e = tid; e < nseq * M; e += nthr) {
     const int sq = e / M, n = e - sq * M, j = n - p;
     const int gr = row0 + sq, c = gr / R, i = gr - c * R;
     float2 v = make_float2(0.f, 0.f);
     if (j >= 0 && j < R) {
-      if (MODE == 0) {
+      if (MODE == 0 && !EX) {
         if (doe_aperture(i, j, R)) {
           const float sv = A.s[(size_t)i * R + j];
           sincosf((c == 0 ? A.kc[0] : c == 1 ? A.kc[1] : A.kc[2]) * (sv * sv), &v.y, &v.x);
         }
+      } else if (MODE == 0) {
+        if (doe_aperture(i, j, R, A.kind)) {                 // (a dead sample loads neither s nor phi)
+          const float sv = A.s[(size_t)i * R + j] + A.eps;
+          float ph = (c == 0 ? A.kc[0] : c == 1 ? A.kc[1] : A.kc[2]) * (sv * sv);
+          if (A.phi) ph += A.phi[(size_t)gr * R + j];
+          sincosf(ph, &v.y, &v.x);
+        }
       } else if (MODE == 1) {
-        if (!A.aperture || doe_aperture(i, j, R)) v = A.field[(size_t)gr * R + j];
-      } else {
+        if (!A.aperture || doe_aperture(i, j, R, A.aperture - 1)) v = A.field[(size_t)gr * R + j];
+      } else if (!EX) {
         const float gq = (float)(((double)A.g[((size_t)c * A.P + i / A.f) * A.P + j / A.f] - dot) * gscale);
+        v = cscale(A.field[(size_t)gr * R + j], gq);
+      } else {
+        const double gs_c = c == 0 ? gscale_c[0] : c == 1 ? gscale_c[1] : gscale_c[2], d_c = c == 0 ? dot_c[0] : c == 1 ? dot_c[1] : dot_c[2];
+        const float gq = (float)(((double)A.g[((size_t)c * A.P + i / A.f) * A.P + j / A.f] - d_c) * gs_c);
         v = cscale(A.field[(size_t)gr * R + j], gq);
       }
     }
@@ -1790,10 +1822,11 @@ __global__ void __launch_bounds__(512) k_doe_cols(float2* __restrict__ Z, const 
 }
 
 // rows: a multiple of f that divides R (a workgroup's rows are whole block rows of one channel).  q == NULL: only w is written
-// (the propagator on its own); w == NULL: no field is kept (no gradient is needed)
+// (the propagator on its own); w == NULL: no field is kept (no gradient is needed).  perch: the last workgroup leaves one sum per
+// channel, stat[2 c] = sum q_c -- gridDim.x / 3 consecutive partials each, because rows divides R -- instead of stat[0] = sum q
 __global__ void k_doe_rows_out(const float2* __restrict__ Z, float2* __restrict__ w, float* __restrict__ q, int R, int p, int f, Plan1D plan,
                                const float2* __restrict__ tw, int rows, double* __restrict__ partial, unsigned* __restrict__ counter,
-                               double* __restrict__ stat) {
+                               double* __restrict__ stat, int perch) {
   HIP_DYNAMIC_SHARED(float2, smem)
   __shared__ double shred[16];
   __shared__ int shlast;
@@ -1833,13 +1866,29 @@ __global__ void k_doe_rows_out(const float2* __restrict__ Z, float2* __restrict_
   if (tid == 0) dpx_st_agent(partial + blockIdx.x, acc);
   if (!dpx_last_block(counter, gridDim.x, &shlast)) return;
   if (tid < 64) {
-    const double S = sum_partials_f64(partial, (int)gridDim.x);
-    if (tid == 0) stat[0] = S;
+    if (!perch) {
+      const double S = sum_partials_f64(partial, (int)gridDim.x);
+      if (tid == 0) stat[0] = S;
+    } else {
+      const int nb = (int)gridDim.x / 3;
+      for (int c = 0; c < 3; ++c) {
+        const double S = sum_partials_f64(partial + c * nb, nb);
+        if (tid == 0) stat[2 * c] = S;
+      }
+    }
   }
 }
 
+struct DoeGradEx {
+  const float* phi;        // EX: [3][R][R] added to the phase, or NULL
+  float eps;               // EX: added to s
+  int kind;                // EX: aperture kind
+  float2* g_field;         // FIELD: [3][R][R]
+  int aperture;            // FIELD: multiply by the aperture (0: no, 1 + kind: yes)
+};
+template <bool EX, bool FIELD>
 __global__ void k_doe_rows_grad(const float2* __restrict__ Z, const float* __restrict__ s, float* __restrict__ gs, float kc0, float kc1, float kc2,
-                                int R, int p, Plan1D plan, const float2* __restrict__ tw, int rows) {
+                                int R, int p, Plan1D plan, const float2* __restrict__ tw, int rows, DoeGradEx X) {
   HIP_DYNAMIC_SHARED(float2, smem)
   const int M = R + 2 * p, ld = M + 1;
   float2* a = smem;
@@ -1854,17 +1903,27 @@ __global__ void k_doe_rows_grad(const float2* __restrict__ Z, const float* __res
   __syncthreads();
   const Twid<float2> twd{tw, M};
   const float2* z = fft_lds<+1, float2>(a, b, plan, twd, 1, nseq, ld, tid, nthr);
+  if (FIELD) {
+    for (int e = tid; e < nseq * R; e += nthr) {
+      const int sq = e / R, j = e - sq * R, rr = sq / 3, c = sq - 3 * rr, i = i0 + rr;
+      const bool live = !X.aperture || doe_aperture(i, j, R, X.aperture - 1);
+      X.g_field[((size_t)c * R + i) * R + j] = live ? z[sq * ld + p + j] : make_float2(0.f, 0.f);
+    }
+    return;
+  }
   const float kc[3] = {kc0, kc1, kc2};
   for (int e = tid; e < nr * R; e += nthr) {
     const int rr = e / R, j = e - rr * R, i = i0 + rr;
     float out = 0.f;
-    if (doe_aperture(i, j, R)) {
-      const float sv = s[(size_t)i * R + j], h = sv * sv;
+    if (EX ? doe_aperture(i, j, R, X.kind) : doe_aperture(i, j, R)) {
+      const float sv = EX ? s[(size_t)i * R + j] + X.eps : s[(size_t)i * R + j], h = sv * sv;
       float t = 0.f;
 #pragma unroll
       for (int c = 0; c < 3; ++c) {
         float sn, cs;
-        sincosf(kc[c] * h, &sn, &cs);
+        float ph = kc[c] * h;
+        if (EX && X.phi) ph += X.phi[((size_t)c * R + i) * R + j];
+        sincosf(ph, &sn, &cs);
         const float2 gu = z[(3 * rr + c) * ld + p + j];
         t = fmaf(kc[c], fmaf(cs, gu.y, -sn * gu.x), t);       // k_c Im(conj(u_c) g_u_c)
       }
@@ -1909,17 +1968,22 @@ int doe_cols_default(int R) { return doe_geom(R, 1).ct_max >= 1 ? 1 : 0; }
 int doe_rows_out_blocks(int R, int f) { return 3 * R / doe_geom(R, f).rows_out; }
 
 int doe_rows_in(int mode, const float* sq, const float2* field, const float* g, const double* stat, const float* kc, int aperture, float2* Z, int R,
-                int f, const void* table, hipStream_t s) {
+                int f, const void* table, hipStream_t s, const DoeEx& E) {
   const DoeGeom G = doe_geom(R, f);
   const Plan1D plan = make_plan(G.M);
-  DoeRowsIn A{sq, field, g, stat, {kc ? kc[0] : 0.f, kc ? kc[1] : 0.f, kc ? kc[2] : 0.f}, aperture, f, R / f};
+  DoeRowsIn A{sq, field, g, stat, {kc ? kc[0] : 0.f, kc ? kc[1] : 0.f, kc ? kc[2] : 0.f}, aperture ? 1 + E.kind : 0, f, R / f, E.phi, E.eps, E.kind};
   const dim3 grid((3 * R + G.rpb_in - 1) / G.rpb_in);
-  if (mode == 0)
-    DPX_LAUNCH_LDS("k_doe_rows_in", k_doe_rows_in<0>, grid, dim3(256), G.sh_in, s, A, Z, R, G.p, plan, tw_rows(table), G.rpb_in);
+  const bool ex0 = E.phi || E.eps != 0.f || E.kind != 0;   // the defaults take the base model's kernels
+  if (mode == 0 && !ex0)
+    DPX_LAUNCH_LDS("k_doe_rows_in", (k_doe_rows_in<0, false>), grid, dim3(256), G.sh_in, s, A, Z, R, G.p, plan, tw_rows(table), G.rpb_in);
+  else if (mode == 0)
+    DPX_LAUNCH_LDS("k_doe_rows_in", (k_doe_rows_in<0, true>), grid, dim3(256), G.sh_in, s, A, Z, R, G.p, plan, tw_rows(table), G.rpb_in);
   else if (mode == 1)
-    DPX_LAUNCH_LDS("k_doe_rows_in", k_doe_rows_in<1>, grid, dim3(256), G.sh_in, s, A, Z, R, G.p, plan, tw_rows(table), G.rpb_in);
+    DPX_LAUNCH_LDS("k_doe_rows_in", (k_doe_rows_in<1, false>), grid, dim3(256), G.sh_in, s, A, Z, R, G.p, plan, tw_rows(table), G.rpb_in);
+  else if (!E.norm)
+    DPX_LAUNCH_LDS("k_doe_rows_in", (k_doe_rows_in<2, false>), grid, dim3(256), G.sh_in, s, A, Z, R, G.p, plan, tw_rows(table), G.rpb_in);
   else
-    DPX_LAUNCH_LDS("k_doe_rows_in", k_doe_rows_in<2>, grid, dim3(256), G.sh_in, s, A, Z, R, G.p, plan, tw_rows(table), G.rpb_in);
+    DPX_LAUNCH_LDS("k_doe_rows_in", (k_doe_rows_in<2, true>), grid, dim3(256), G.sh_in, s, A, Z, R, G.p, plan, tw_rows(table), G.rpb_in);
   return launch_status("doe_rows_in");
 }
 
@@ -1936,20 +2000,35 @@ int doe_cols(float2* Z, const float2* H, int conj, int R, int ct, const void* ta
 }
 
 int doe_rows_out(const float2* Z, float2* w, float* q, double* partial, unsigned* counter, double* stat, int R, int f, const void* table,
-                 hipStream_t s) {
+                 hipStream_t s, int perch) {
   const DoeGeom G = doe_geom(R, f);
   const Plan1D plan = make_plan(G.M);
   DPX_LAUNCH_LDS("k_doe_rows_out", k_doe_rows_out, dim3(3 * R / G.rows_out), dim3(256), G.sh_out, s, Z, w, q, R, G.p, f, plan, tw_rows(table),
-                 G.rows_out, partial, counter, stat);
+                 G.rows_out, partial, counter, stat, perch);
   return launch_status("doe_rows_out");
 }
 
-int doe_rows_grad(const float2* Z, const float* sq, float* gs, const float* kc, int R, const void* table, hipStream_t s) {
+int doe_rows_grad(const float2* Z, const float* sq, float* gs, const float* kc, int R, const void* table, hipStream_t s, const DoeEx& E) {
   const DoeGeom G = doe_geom(R, 1);
   const Plan1D plan = make_plan(G.M);
-  DPX_LAUNCH_LDS("k_doe_rows_grad", k_doe_rows_grad, dim3((R + G.rows_grad - 1) / G.rows_grad), dim3(256), G.sh_grad, s, Z, sq, gs, kc[0], kc[1],
-                 kc[2], R, G.p, plan, tw_rows(table), G.rows_grad);
+  const DoeGradEx X{E.phi, E.eps, E.kind, nullptr, 0};
+  const dim3 grid((R + G.rows_grad - 1) / G.rows_grad);
+  if (E.phi || E.eps != 0.f || E.kind != 0)
+    DPX_LAUNCH_LDS("k_doe_rows_grad", (k_doe_rows_grad<true, false>), grid, dim3(256), G.sh_grad, s, Z, sq, gs, kc[0], kc[1], kc[2], R, G.p, plan,
+                   tw_rows(table), G.rows_grad, X);
+  else
+    DPX_LAUNCH_LDS("k_doe_rows_grad", (k_doe_rows_grad<false, false>), grid, dim3(256), G.sh_grad, s, Z, sq, gs, kc[0], kc[1], kc[2], R, G.p, plan,
+                   tw_rows(table), G.rows_grad, X);
   return launch_status("doe_rows_grad");
+}
+
+int doe_rows_grad_field(const float2* Z, float2* g_field, int aperture, int kind, int R, const void* table, hipStream_t s) {
+  const DoeGeom G = doe_geom(R, 1);
+  const Plan1D plan = make_plan(G.M);
+  const DoeGradEx X{nullptr, 0.f, 0, g_field, aperture ? 1 + kind : 0};
+  DPX_LAUNCH_LDS("k_doe_rows_grad", (k_doe_rows_grad<false, true>), dim3((R + G.rows_grad - 1) / G.rows_grad), dim3(256), G.sh_grad, s, Z,
+                 (const float*)nullptr, (float*)nullptr, 0.f, 0.f, 0.f, R, G.p, plan, tw_rows(table), G.rows_grad, X);
+  return launch_status("doe_rows_grad_field");
 }
 
 }  // namespace dpx

@@ -74,16 +74,27 @@ int doe_cols_default(int R);                // ... and the number the library la
 int doe_rows_out_blocks(int R, int f);      // workgroups of doe_rows_out = partial sums it hands to its last workgroup
 // mode 0: u_c = a exp(i kc[c] sq^2) from the height map's square root sq [R][R]; 1: `field` [3][R][R] (times the aperture a if asked);
 // 2: the backward pass's g_w from field = w, the psf's cotangent g [3][R / f][R / f] and stat = (sum q, <g, psf>).  kc: host, 3 values
+// E: the hybrid model's generalisation -- u_c = a exp(i (kc[c] (sq + eps)^2 + phi_c)) with phi [3][R][R] (nullable), the aperture kind
+// (0: the disc, 1: its right half, which mode 1's `aperture` follows too) and, in mode 2, one normalisation per channel (norm = 1:
+// stat[2 c] = sum q_c, stat[2 c + 1] = <g_c, psf_c>).  The defaults launch the base model's kernels.
+struct DoeEx {
+  const float* phi = nullptr;
+  float eps = 0.f;
+  int kind = 0;
+  int norm = 0;
+};
 int doe_rows_in(int mode, const float* sq, const float2* field, const float* g, const double* stat, const float* kc, int aperture, float2* Z, int R,
-                int f, const void* table, hipStream_t s);
+                int f, const void* table, hipStream_t s, const DoeEx& E = DoeEx());
 // H: [3][M][M] with the inverse transforms' 1 / M^2 folded in; conj: multiply by its conjugate; ct: columns per workgroup
 int doe_cols(float2* Z, const float2* H, int conj, int R, int ct, const void* table, hipStream_t s);
 // w [3][R][R] (nullable) = the propagated field; q [3][R / f][R / f] (nullable) = block mean of |w|^2, stat[0] = its sum (partial:
-// doe_rows_out_blocks doubles, counter: one zeroed ticket)
+// doe_rows_out_blocks doubles, counter: one zeroed ticket); perch: stat[2 c] = the sum of channel c instead
 int doe_rows_out(const float2* Z, float2* w, float* q, double* partial, unsigned* counter, double* stat, int R, int f, const void* table,
-                 hipStream_t s);
-// gs [R][R] = 2 sq sum_c kc[c] Im(conj(u_c) g_u_c) on the aperture, 0 outside
-int doe_rows_grad(const float2* Z, const float* sq, float* gs, const float* kc, int R, const void* table, hipStream_t s);
+                 hipStream_t s, int perch = 0);
+// gs [R][R] = 2 (sq + eps) sum_c kc[c] Im(conj(u_c) g_u_c) on the aperture, 0 outside
+int doe_rows_grad(const float2* Z, const float* sq, float* gs, const float* kc, int R, const void* table, hipStream_t s, const DoeEx& E = DoeEx());
+// g_field [3][R][R] = the cotangent g_u itself (dL/dRe + i dL/dIm), times the aperture of `kind` if asked
+int doe_rows_grad_field(const float2* Z, float2* g_field, int aperture, int kind, int R, const void* table, hipStream_t s);
 
 // ---- dpx_fft_pow2.hip: transforms of the power-of-two planes (pow2_path_available) -------------------------
 size_t pow2_spec_elems(int P, int H, int W);

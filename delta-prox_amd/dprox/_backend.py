@@ -55,6 +55,12 @@ class BwdTerm(ctypes.Structure):
                 ("lam", c_void_p), ("v", c_void_p), ("gv", c_void_p), ("gu_new", c_void_p), ("gu", c_void_p)]
 
 
+class DoeOpts(ctypes.Structure):
+    """``dpx_doe_opts`` of include/dpx.h."""
+    _fields_ = [("eps", c_float), ("aperture_kind", c_int32), ("norm_mode", c_int32), ("reserved", c_int32), ("phi", c_void_p), ("gs", c_void_p),
+                ("g_field", c_void_p)]
+
+
 # name -> (restype, argtypes); every symbol include/dpx.h declares
 SIGNATURES = {
     "dpx_version": (c_int, []),
@@ -274,6 +280,13 @@ SIGNATURES = {
                                      c_int, c_void_p, c_void_p]),
     "dpx_doe_propagate": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
     "dpx_doe_phase": (c_int, [c_void_p, c_int, POINTER(c_double), POINTER(c_double), c_void_p, c_long, c_void_p]),
+    "dpx_doe_psf_ex": (c_int, [c_void_p, c_void_p, POINTER(c_double), POINTER(c_double), c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
+                               POINTER(DoeOpts), c_void_p, c_void_p]),
+    "dpx_doe_psf_backward_ex": (c_int, [c_void_p, c_void_p, c_void_p, POINTER(c_double), POINTER(c_double), c_void_p, c_void_p, c_int, c_int, c_int,
+                                        POINTER(DoeOpts), c_void_p, c_void_p]),
+    "dpx_doe_propagate_backward": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
+    "dpx_doe_phase_ex": (c_int, [c_void_p, c_int, c_float, c_void_p, POINTER(c_double), POINTER(c_double), c_void_p, c_long, c_void_p]),
+    "dpx_doe_phase_backward": (c_int, [c_void_p, c_void_p, c_int, c_float, c_void_p, POINTER(c_double), POINTER(c_double), c_void_p, c_long, c_void_p]),
 }
 
 

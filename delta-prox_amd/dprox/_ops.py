@@ -1527,14 +1527,37 @@ def doe_context(R, P, distance, interval, wave_lengths, refractive_idcs, device)
     return c
 
 
-def _doe_forward(doe, s, profile, keep_field):
+class DoeOptions:
+    """the hybrid model's generalisation of the DOE kernels (``dpx_doe_opts``): u_c = a exp(i (k_c (s + eps)^2 + phi_c)) with an optional
+    fp32 plane phi [1, 3, R, R], the aperture kind (0 circular, 1 half-circular) and the normalisation (0: one sum over the three
+    channels, 1: one per channel).  ``None`` in its place is the base model, which runs the kernels it always ran."""
+
+    def __init__(self, eps=0.0, phi=None, aperture_kind=0, norm_mode=0):
+        self.eps, self.phi, self.aperture_kind, self.norm_mode = float(eps), phi, int(aperture_kind), int(norm_mode)
+
+    def block(self, doe, gs=None, g_field=None):
+        phi = self.phi
+        if phi is not None:
+            if not isinstance(phi, torch.Tensor) or phi.dtype != torch.float32 or tuple(phi.shape) != (1, 3, doe.R, doe.R):
+                raise ValueError(f"DOE model: the phase plane must be a float32 tensor of shape {(1, 3, doe.R, doe.R)}")
+            require(phi, what="DOE model phase plane")
+        addr = lambda t: None if t is None else t.data_ptr()
+        return be.DoeOpts(self.eps, self.aperture_kind, self.norm_mode, 0, addr(phi), addr(gs), addr(g_field))
+
+
+def _doe_forward(doe, s, profile, keep_field, opt=None):
     """one dpx_doe_psf call on checked operands: (psf [1, 3, P, P], the workspace -- the caller's to keep when it holds the field)"""
     L = be.lib()
     nb = doe.ws_bytes(keep_field)
     ws = _bytes(nb, doe.device) if keep_field else workspace("doe", nb, doe.device)
     psf = torch.empty(1, 3, doe.P, doe.P, dtype=torch.float32, device=doe.device)
-    L.call("dpx_doe_psf", ptr(s), ptr(profile), doe.wl, doe.ri, ptr(psf), ptr(doe.H), ptr(doe.table), doe.R, doe.P, int(keep_field), doe.cols_per_wg,
-           ptr(ws), be.stream())
+    if opt is None and not (keep_field and profile is not None):
+        L.call("dpx_doe_psf", ptr(s), ptr(profile), doe.wl, doe.ri, ptr(psf), ptr(doe.H), ptr(doe.table), doe.R, doe.P, int(keep_field),
+               doe.cols_per_wg, ptr(ws), be.stream())
+    else:
+        block = (opt or DoeOptions()).block(doe)
+        L.call("dpx_doe_psf_ex", ptr(s), ptr(profile), doe.wl, doe.ri, ptr(psf), ptr(doe.H), ptr(doe.table), doe.R, doe.P, int(keep_field),
+               doe.cols_per_wg, ctypes.byref(block), ptr(ws), be.stream())
     doe.last_ws_bytes = nb
     return psf, ws
 
@@ -1543,10 +1566,10 @@ class _DoePsfFn(torch.autograd.Function):
     """ops.doe_psf under autograd: the forward keeps the propagated field in a workspace of its own, dpx_doe_psf_backward reads it"""
 
     @staticmethod
-    def forward(ctx, s, doe):
+    def forward(ctx, s, doe, opt):
         sd = s.detach()
-        psf, ws = _doe_forward(doe, sd, None, True)
-        ctx.doe, ctx.ws = doe, ws
+        psf, ws = _doe_forward(doe, sd, None, True, opt)
+        ctx.doe, ctx.ws, ctx.opt = doe, ws, opt
         ctx.save_for_backward(sd, psf)
         return psf
 
@@ -1556,9 +1579,38 @@ class _DoePsfFn(torch.autograd.Function):
         doe = ctx.doe
         g = require(g.contiguous(), what="doe_psf cotangent")
         gs = torch.empty_like(s)
-        be.lib().call("dpx_doe_psf_backward", ptr(g), ptr(psf), ptr(s), doe.wl, doe.ri, ptr(gs), ptr(doe.H), ptr(doe.table), doe.R, doe.P,
-                      doe.cols_per_wg, ptr(ctx.ws), be.stream())
-        return gs, None
+        if ctx.opt is None:
+            be.lib().call("dpx_doe_psf_backward", ptr(g), ptr(psf), ptr(s), doe.wl, doe.ri, ptr(gs), ptr(doe.H), ptr(doe.table), doe.R, doe.P,
+                          doe.cols_per_wg, ptr(ctx.ws), be.stream())
+        else:
+            block = ctx.opt.block(doe, gs=gs)
+            be.lib().call("dpx_doe_psf_backward_ex", ptr(g), ptr(psf), ptr(s), doe.wl, doe.ri, ptr(doe.H), ptr(doe.table), doe.R, doe.P,
+                          doe.cols_per_wg, ctypes.byref(block), ptr(ctx.ws), be.stream())
+        return gs, None, None
+
+
+class _DoePsfProfileFn(torch.autograd.Function):
+    """ops.doe_psf_of_profile under autograd: the backward pass stores the cotangent of the field in front of the propagator, times the
+    aperture -- the gradient to the profile, dL/dRe + i dL/dIm"""
+
+    @staticmethod
+    def forward(ctx, prof, doe, opt):
+        pd = prof.detach()
+        psf, ws = _doe_forward(doe, None, pd, True, opt)
+        ctx.doe, ctx.ws, ctx.opt = doe, ws, opt
+        ctx.save_for_backward(psf)
+        return psf
+
+    @staticmethod
+    def backward(ctx, g):
+        (psf,) = ctx.saved_tensors
+        doe = ctx.doe
+        g = require(g.contiguous(), what="doe_psf cotangent")
+        gp = torch.empty(1, 3, doe.R, doe.R, dtype=torch.complex64, device=doe.device)
+        block = (ctx.opt or DoeOptions()).block(doe, g_field=gp)
+        be.lib().call("dpx_doe_psf_backward_ex", ptr(g), ptr(psf), None, None, None, ptr(doe.H), ptr(doe.table), doe.R, doe.P, doe.cols_per_wg,
+                      ctypes.byref(block), ptr(ctx.ws), be.stream())
+        return gp, None, None
 
 
 def _doe_check(t, doe, channels, dtype, what):
@@ -1571,39 +1623,106 @@ def _doe_check(t, doe, channels, dtype, what):
     return require(t.contiguous(), dtype=dtype, what=what)
 
 
-def doe_psf(doe, s):
+def doe_psf(doe, s, opt=None):
     """psf [1, 3, P, P] of the height map s^2 for s = height_map_sqrt [1, 1, R, R] fp32 (RGBCollimator.get_psf of the reference): three
     transform launches + one normalising launch; differentiable in s (dpx_doe_psf_backward).  A call that needs no gradient keeps no
-    field."""
+    field.  opt: a DoeOptions (the hybrid model); None = the base model."""
     s = _doe_check(s, doe, 1, torch.float32, "doe_psf height_map_sqrt")
     if torch.is_grad_enabled() and s.requires_grad:
-        return _DoePsfFn.apply(s, doe)
-    return _doe_forward(doe, s.detach(), None, False)[0]
+        return _DoePsfFn.apply(s, doe, opt)
+    return _doe_forward(doe, s.detach(), None, False, opt)[0]
 
 
 def doe_psf_from_profile(doe, phase_profile):
-    """the same psf from an explicit complex64 phase profile [1, 3, R, R] (multiplied by the aperture); forward only"""
+    """the base model's psf from an explicit complex64 phase profile [1, 3, R, R] (multiplied by the aperture); forward only --
+    doe_psf_of_profile is the differentiable form"""
     if isinstance(phase_profile, torch.Tensor) and phase_profile.requires_grad and torch.is_grad_enabled():
-        raise NotImplementedError("doe_psf: the gradient with respect to an explicit phase_profile is not built (train height_map_sqrt, or "
-                                  "detach the profile)")
+        raise NotImplementedError("doe_psf_from_profile: forward only; the gradient with respect to an explicit phase_profile is "
+                                  "doe_psf_of_profile's (RGBCollimator.get_psf(phase_profile) goes through it)")
+    return doe_psf_of_profile(doe, phase_profile)
+
+
+def doe_psf_of_profile(doe, phase_profile, opt=None):
+    """the psf from an explicit complex64 phase profile [1, 3, R, R] (multiplied by the aperture); differentiable in the profile
+    (dpx_doe_psf_backward_ex with g_field).  opt: a DoeOptions (the hybrid model); None = the base model."""
     prof = _doe_check(phase_profile, doe, 3, torch.complex64, "doe_psf phase_profile")
-    return _doe_forward(doe, None, prof.detach(), False)[0]
+    if torch.is_grad_enabled() and prof.requires_grad:
+        return _DoePsfProfileFn.apply(prof, doe, opt)
+    return _doe_forward(doe, None, prof.detach(), False, opt)[0]
 
 
-def doe_propagate(doe, field):
-    """crop(ifft2(fft2(zero-pad(field)) . H)) of a complex64 field [1, 3, R, R] (FresnelPropagator.forward of the reference); forward only"""
-    if isinstance(field, torch.Tensor) and field.requires_grad and torch.is_grad_enabled():
-        raise NotImplementedError("FresnelPropagator: the gradient with respect to an explicit field is not built")
-    field = _doe_check(field, doe, 3, torch.complex64, "doe_propagate field").detach()
+def _doe_propagate(doe, field, backward):
     out = torch.empty_like(field)
     L = be.lib()
     ws = workspace("doe", L.query("dpx_doe_ws_bytes", doe.R, doe.R, 0), doe.device)
-    L.call("dpx_doe_propagate", ptr(field), ptr(out), ptr(doe.H), ptr(doe.table), doe.R, doe.cols_per_wg, ptr(ws), be.stream())
+    L.call("dpx_doe_propagate_backward" if backward else "dpx_doe_propagate", ptr(field), ptr(out), ptr(doe.H), ptr(doe.table), doe.R,
+           doe.cols_per_wg, ptr(ws), be.stream())
     return out
 
 
-def doe_phase(x, squared, wave_lengths, refractive_idcs):
-    """exp(i k_c h) as complex64 [1, 3, H, W] for h = x^2 (squared) or x, x fp32 with H W elements ([H, W] .. [1, 1, H, W]); forward only"""
+class _DoePropagateFn(torch.autograd.Function):
+    """ops.doe_fresnel under autograd: the operator is linear, its backward is its adjoint on the cotangent (dpx_doe_propagate_backward)"""
+
+    @staticmethod
+    def forward(ctx, field, doe):
+        ctx.doe = doe
+        return _doe_propagate(doe, field.detach(), False)
+
+    @staticmethod
+    def backward(ctx, g):
+        g = require(g.contiguous(), dtype=torch.complex64, what="doe_propagate cotangent")
+        return _doe_propagate(ctx.doe, g, True), None
+
+
+def doe_propagate(doe, field):
+    """crop(ifft2(fft2(zero-pad(field)) . H)) of a complex64 field [1, 3, R, R]; forward only -- doe_fresnel is the differentiable form"""
+    if isinstance(field, torch.Tensor) and field.requires_grad and torch.is_grad_enabled():
+        raise NotImplementedError("doe_propagate: forward only; the gradient with respect to an explicit field is doe_fresnel's "
+                                  "(FresnelPropagator.forward goes through it)")
+    return doe_fresnel(doe, field)
+
+
+def doe_fresnel(doe, field):
+    """crop(ifft2(fft2(zero-pad(field)) . H)) of a complex64 field [1, 3, R, R] (FresnelPropagator.forward of the reference);
+    differentiable in the field (dpx_doe_propagate_backward)"""
+    field = _doe_check(field, doe, 3, torch.complex64, "doe_propagate field")
+    if torch.is_grad_enabled() and field.requires_grad:
+        return _DoePropagateFn.apply(field, doe)
+    return _doe_propagate(doe, field.detach(), False)
+
+
+class _DoePhaseFn(torch.autograd.Function):
+    """ops.doe_phase under autograd: dpx_doe_phase_backward recomputes the profile"""
+
+    @staticmethod
+    def forward(ctx, x, squared, eps, offset, wl, ri):
+        xd = x.detach()
+        ctx.args = (squared, eps, offset, wl, ri)
+        ctx.save_for_backward(xd)
+        return _doe_phase(xd, squared, eps, offset, wl, ri)
+
+    @staticmethod
+    def backward(ctx, g):
+        (x,) = ctx.saved_tensors
+        squared, eps, offset, wl, ri = ctx.args
+        g = require(g.contiguous(), dtype=torch.complex64, what="doe_phase cotangent")
+        gx = torch.empty_like(x)
+        be.lib().call("dpx_doe_phase_backward", ptr(g), ptr(x), int(squared), c_float(eps), ptr(offset), wl, ri, ptr(gx), x.numel(), be.stream())
+        return gx, None, None, None, None, None
+
+
+def _doe_phase(x, squared, eps, offset, wl, ri):
+    out = torch.empty(1, 3, int(x.shape[-2]), int(x.shape[-1]), dtype=torch.complex64, device=x.device)
+    if eps == 0.0 and offset is None:
+        be.lib().call("dpx_doe_phase", ptr(x), int(squared), wl, ri, ptr(out), x.numel(), be.stream())
+    else:
+        be.lib().call("dpx_doe_phase_ex", ptr(x), int(squared), c_float(eps), ptr(offset), wl, ri, ptr(out), x.numel(), be.stream())
+    return out
+
+
+def doe_phase(x, squared, wave_lengths, refractive_idcs, eps=0.0, offset=None):
+    """exp(i (k_c h + offset_c)) as complex64 [1, 3, H, W] for h = (x + eps)^2 (squared) or x, x fp32 with H W elements ([H, W] ..
+    [1, 1, H, W]); offset: an optional fp32 plane [1, 3, H, W].  Differentiable in x (dpx_doe_phase_backward)."""
     if not isinstance(x, torch.Tensor):
         raise be.DpxError(f"doe_phase: expected a torch.Tensor, got {type(x)}")
     if x.dtype != torch.float32:
@@ -1611,7 +1730,11 @@ def doe_phase(x, squared, wave_lengths, refractive_idcs):
     if x.ndim < 2 or x.numel() != int(x.shape[-2]) * int(x.shape[-1]) or x.numel() < 1:
         raise ValueError(f"doe_phase: a height map of shape {tuple(x.shape)} (one plane: [H, W] .. [1, 1, H, W])")
     wl, ri = _three_doubles(wave_lengths, "wave lengths"), _three_doubles(refractive_idcs, "refractive indices")
-    x = require(x.detach().contiguous(), what="doe_phase height map")
-    out = torch.empty(1, 3, int(x.shape[-2]), int(x.shape[-1]), dtype=torch.complex64, device=x.device)
-    be.lib().call("dpx_doe_phase", ptr(x), int(bool(squared)), wl, ri, ptr(out), x.numel(), be.stream())
-    return out
+    if offset is not None:
+        if not isinstance(offset, torch.Tensor) or offset.dtype != torch.float32 or tuple(offset.shape) != (1, 3, int(x.shape[-2]), int(x.shape[-1])):
+            raise ValueError(f"doe_phase: the phase offset must be a float32 tensor of shape {(1, 3, int(x.shape[-2]), int(x.shape[-1]))}")
+        offset = require(offset.detach().to(x.device).contiguous(), what="doe_phase offset")
+    xc = require(x.contiguous(), what="doe_phase height map")
+    if torch.is_grad_enabled() and xc.requires_grad:
+        return _DoePhaseFn.apply(xc, bool(squared), float(eps), offset, wl, ri)
+    return _doe_phase(xc.detach(), bool(squared), float(eps), offset, wl, ri)

@@ -93,7 +93,7 @@ class FresnelPropagator(nn.Module):
         return self._context().H
 
     def forward(self, input_field):
-        return ops.doe_propagate(self._context(), input_field)
+        return ops.doe_fresnel(self._context(), input_field)
 
 
 def get_one_phase_shift_thickness(wave_lengths, refractive_index):

@@ -35,12 +35,14 @@ class HeightMap(nn.Module):
 
     def get_phase_profile(self, height_map=None):
         """exp(i k_c (n_c - 1) h) as complex64 [1, 3, R, R] for h = ``height_map`` (one plane), by default height_map_sqrt^2: one small
-        kernel (``dpx_doe_phase``), forward only -- ``RGBCollimator.get_psf()`` is the differentiable path"""
+        kernel (``dpx_doe_phase``).  An explicit height map that requires a gradient raises here, as it always has: its differentiable
+        form is ``ops.doe_phase(height_map, False, wave_lengths, refractive_idcs)`` (``dpx_doe_phase_backward``), which the hybrid
+        model's ``HeightMap`` uses.  ``RGBCollimator.get_psf()`` never forms this profile in memory."""
         if height_map is None:
             return ops.doe_phase(self.height_map_sqrt, True, self.wave_lengths, self.refractive_idcs)
         if isinstance(height_map, torch.Tensor) and height_map.requires_grad and torch.is_grad_enabled():
-            raise NotImplementedError("get_phase_profile: the gradient with respect to an explicit height map is not built "
-                                      "(RGBCollimator.get_psf() differentiates height_map_sqrt)")
+            raise NotImplementedError("get_phase_profile: the gradient with respect to an explicit height map is ops.doe_phase's "
+                                      "(this method is forward only for an explicit argument)")
         return ops.doe_phase(height_map, False, self.wave_lengths, self.refractive_idcs)
 
     def phase_to_height_map(self, phi, wave_length_idx=1):
@@ -74,10 +76,10 @@ class RGBCollimator(nn.Module):
     def get_psf(self, phase_profile=None):
         """PSF [1, 3, patch, patch] of the element, normalised to sum 1 over all three channels.  Without an argument: from
         ``height_map_sqrt``, differentiable.  With a complex64 ``phase_profile`` [1, 3, R, R]: that profile behind the aperture,
-        forward only (a profile that requires a gradient raises)."""
+        differentiable in the profile."""
         if phase_profile is None:
             return ops.doe_psf(self._context(), self.height_map.height_map_sqrt)
-        return ops.doe_psf_from_profile(self._context(), phase_profile)
+        return ops.doe_psf_of_profile(self._context(), phase_profile)
 
     def forward(self, input_img, phase_profile=None, circular=False):
         psfs = self.get_psf(phase_profile)

@@ -944,6 +944,40 @@ int dpx_doe_psf_backward(const float* g, const float* psf, const float* s, const
 int dpx_doe_propagate(const void* field, void* out, const void* H, const void* table, int R, int cols_per_wg, void* ws, dpx_stream_t stream);
 int dpx_doe_phase(const float* x, int squared, const double* wave_lengths, const double* refractive_idcs, void* out, long n, dpx_stream_t stream);
 
+/* The hybrid model (a refractive lens plus the element: contrib/optic/doe_model_hybrid.py) and the gradients to explicit arguments: the
+ * same launches, generalised by one options block.  A NULL block, or a zeroed one, is the base model and runs its kernels.
+ *   u_c = a exp(i (k_c (s + eps)^2 + phi_c)),  a: the disc (aperture_kind 0) or its right half (1: additionally 2 j - (R-1) > 0, j the
+ *   column),  psf = q / sum_{c,y,x} q (norm_mode 0) or psf_c = q_c / sum_{y,x} q_c (norm_mode 1)
+ *   dpx_doe_psf_ex             dpx_doe_psf under these options; with a phase_profile, keep_field = 1 keeps its propagated field too
+ *   dpx_doe_psf_backward_ex    the options of the forward call plus ONE output: gs [R][R], the gradient to s, or g_field [3][R][R]
+ *                              complex64, the gradient to the explicit phase profile of the forward call (s, wave_lengths and
+ *                              refractive_idcs may then be NULL)
+ *   dpx_doe_propagate_backward g_field [3][R][R] = the adjoint of dpx_doe_propagate applied to g_out [3][R][R]; ws as dpx_doe_propagate
+ *   dpx_doe_phase_ex           out [3][n] = exp(i (k_c h + offset_c)), h = (x + eps)^2 (squared = 1) or x; offset [3][n] fp32 or NULL
+ *   dpx_doe_phase_backward     gx [n] = sum_c k_c Im(conj(out_c) g_c), times 2 (x + eps) when squared; out is recomputed
+ * Complex cotangents and gradients follow the convention of a real loss L: dL/dRe + i dL/dIm.  Workspaces: dpx_doe_ws_bytes.  The same
+ * argument-error contract: an unknown aperture_kind / norm_mode, a negative eps, both or neither output -> DPX_ERR_ARG, nothing launched. */
+typedef struct dpx_doe_opts {
+  float eps;              /* added to s in float32 before the square: 0 (base model), 1e-7f (hybrid)          */
+  int aperture_kind;      /* 0: circular, 1: half-circular                                                    */
+  int norm_mode;          /* 0: one sum over the three channels, 1: one per channel                           */
+  int reserved;           /* 0                                                                                */
+  const float* phi;       /* [3][R][R] fp32 added to the phase, or NULL                                       */
+  float* gs;              /* dpx_doe_psf_backward_ex: the gradient to s [R][R], or NULL                       */
+  void* g_field;          /* dpx_doe_psf_backward_ex: the gradient to the phase profile [3][R][R], or NULL    */
+} dpx_doe_opts;
+int dpx_doe_psf_ex(const float* s, const void* phase_profile, const double* wave_lengths, const double* refractive_idcs, float* psf, const void* H,
+                   const void* table, int R, int P, int keep_field, int cols_per_wg, const dpx_doe_opts* opts, void* ws, dpx_stream_t stream);
+int dpx_doe_psf_backward_ex(const float* g, const float* psf, const float* s, const double* wave_lengths, const double* refractive_idcs,
+                            const void* H, const void* table, int R, int P, int cols_per_wg, const dpx_doe_opts* opts, void* ws,
+                            dpx_stream_t stream);
+int dpx_doe_propagate_backward(const void* g_out, void* g_field, const void* H, const void* table, int R, int cols_per_wg, void* ws,
+                               dpx_stream_t stream);
+int dpx_doe_phase_ex(const float* x, int squared, float eps, const float* offset, const double* wave_lengths, const double* refractive_idcs, void* out,
+                     long n, dpx_stream_t stream);
+int dpx_doe_phase_backward(const void* g, const float* x, int squared, float eps, const float* offset, const double* wave_lengths,
+                           const double* refractive_idcs, float* gx, long n, dpx_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
