@@ -28,6 +28,7 @@ def _hip_lib_loaded():
 
 
 import deq_cases as dc  # noqa: E402
+import fft_cases as fc  # noqa: E402
 import minres_cases as mc  # noqa: E402
 import nlm_cases as nc  # noqa: E402
 import parity_cases as pc  # noqa: E402
@@ -87,6 +88,8 @@ RUNS = {
     "minres_step_f64_preconditioned": (mc.case_step, ((2, 33, 3), torch.float64), dict(prec=True)),
     "minres_linear_solve": (mc.case_linear_solve, (), {}),
     "nlm_admm_fused": (nc.case_admm, ("admm", True), {}),
+    # every FFT path against float64 with flat-spectrum operators (cases A and B of tests/fft_cases.py)
+    **{f"fft_{fc.sid(s)}": (fc.case_guarded, (s,), {}) for s in fc.GUARDED},
 }
 
 
